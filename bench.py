@@ -1,6 +1,16 @@
 """Env-steps/sec of the full VecTask.step hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--task Gogoro] [--num-envs 4096]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, steps W warm-up and K timed steps, and prints the result
+line: ``value``, ``ms_per_step`` and the workload it ran.  ``--dump-outputs
+DIR`` then writes what the last timed ``env.step`` returned (obs, rew, reset,
+time_outs; states when the task has them) as float32 ``DIR/<name>.npy`` -- the
+env seed and the action pool are fixed, so two builds can be compared output
+for output.  ``--full`` adds what takes work of its own: the step kernel's
+event timing and the roofline block built on it, and the CPU baselines (a
+plain run records no event in its timed region).
 
 One process per GPU: under torchrun RANK/LOCAL_RANK/WORLD_SIZE come from the
 env (WORLD_SIZE must equal --gpus); a plain ``python bench.py --gpus N`` with
@@ -11,7 +21,7 @@ reward, masked resets, timeouts) -- inputs resident in HBM, synthetic
 actions U(-1,1) from torch.Generator(seed 1234 + rank).  Rank 0 prints one
 JSON line; ``value`` = envs x steps x ranks / max-over-ranks wall time.
 
-Roofline: the dominant kernel is the articulation step kernel
+Roofline (``--full``): the dominant kernel is the articulation step kernel
 (tg::step_par_kernel, all substeps of one simulate() in one launch).  For the
 one-launch steps (ThormangWalk*, Gogoro) the library brackets windows of
 TIMING_WINDOW consecutive step-kernel launches with one HIP event pair on the
@@ -24,7 +34,7 @@ algorithmic bytes per env-step
 HBM rate against the 8 TB/s MI355X peak.  ``traffic`` is the PMC-measured HBM
 bytes per launch of the same kernel from a committed rocprofv3 summary
 (scripts/gpu_profile.sh + scripts/pmc_summary.py) when one exists for this
-workload, else null.  cpu_baseline: the CPU oracle env (oracle/: the same physics
+workload, else null.  cpu_baseline (``--full``): the CPU oracle env (oracle/: the same physics
 + task algorithm, OpenMP) on a bounded sample of the same workload, rank 0
 only: its fp32 build (the GPU's arithmetic type) as the value, the fp64 parity
 oracle beside it.
@@ -289,6 +299,32 @@ def launch_ranks(n: int, argv: list[str]) -> int:
     return subprocess.call(cmd)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, result, rank: int, world: int) -> None:
+    """Write what ``env.step`` returned -- (obs_dict, rew, reset, extras) -- as
+    float32 ``<name>.npy`` files (``<name>_rank<r>.npy`` with more than one
+    rank).  Past DUMP_LIMIT_BYTES in all, every array keeps the same seeded
+    sample of its env rows."""
+    obs_dict, rew, reset, extras = result
+    arrays = {"obs": obs_dict["obs"], "rew": rew, "reset": reset, "time_outs": extras["time_outs"]}
+    if "states" in obs_dict:
+        arrays["states"] = obs_dict["states"]
+    arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = arrays["rew"].shape[0]
+        keep = max(1, int(n * DUMP_LIMIT_BYTES // total))
+        rows = np.sort(np.random.default_rng(20240229).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["env_rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), np.ascontiguousarray(a))
+
+
 def stub_run(args, world: int, rank: int, local: int, rccl_world):
     """TG_BENCH_STUB=1: the launch / rank / timing path with a sleep in place of
     env.step and no GPU (CPU tests only; never a measured line)."""
@@ -313,7 +349,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--task", default="ThormangWalk")
     ap.add_argument("--num-envs", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the step kernel (roofline block) and run the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--solver-type", type=int, choices=(0, 1), default=None,
                     help="override the task cfg's sim.physx.solver_type (0 PGS, 1 TGS) for an A/B line")
     ap.add_argument("--contact-offset", type=float, default=None,
@@ -383,51 +423,49 @@ def main():
     pool = torch.rand(min(args.steps + args.warmup, 512), N, acts, device=dev, generator=gen) * 2 - 1
     it = [0]
 
+    last = [None]
+
     def step():
         a = pool[it[0] % pool.shape[0]]
         it[0] += 1
-        return env.step(a)
+        last[0] = env.step(a)
 
     for _ in range(args.warmup):
         step()
-    env.sim.read_kernel_timing()
     windowed = args.task in ONE_LAUNCH_TASKS
-    env.sim.set_kernel_timing(-TIMING_WINDOW if windowed else TIMING_PERIOD)
+    if args.full:
+        env.sim.read_kernel_timing()
+        env.sim.set_kernel_timing(-TIMING_WINDOW if windowed else TIMING_PERIOD)
     elapsed = timed_region(step, args.steps, world, dev if backend == "nccl" else "cpu", torch.cuda.synchronize)
-    # a short timed region (the driver's --steps 20) samples only a launch or
-    # two: keep stepping, after the clock has stopped, until MIN_KERNEL_SAMPLES
-    # launches are timed, so kernel_ms is never a one- or two-sample figure
-    extra = 0
-    while (args.steps + extra < MIN_KERNEL_SAMPLES + 2 * TIMING_WINDOW if windowed
-           else (args.steps + extra) // TIMING_PERIOD < MIN_KERNEL_SAMPLES):
-        step()
-        extra += 1
-    torch.cuda.synchronize()
-    env.sim.set_kernel_timing(0)
-    tot_ms, launches = env.sim.read_kernel_timing()
-    if launches == 0 and windowed:   # every window had another launch in it: time launches one by one
-        windowed = False
-        env.sim.set_kernel_timing(TIMING_PERIOD)
-        for _ in range(MIN_KERNEL_SAMPLES * TIMING_PERIOD):
+    if args.dump_outputs and args.steps > 0:   # before any further step overwrites the live buffers
+        dump_outputs(args.dump_outputs, last[0], rank, world)
+    kern_ms = launches = extra = None
+    if args.full:
+        # a short timed region (--steps 20) samples only a launch or two: keep
+        # stepping, after the clock has stopped, until MIN_KERNEL_SAMPLES
+        # launches are timed, so kernel_ms is never a one- or two-sample figure
+        extra = 0
+        while (args.steps + extra < MIN_KERNEL_SAMPLES + 2 * TIMING_WINDOW if windowed
+               else (args.steps + extra) // TIMING_PERIOD < MIN_KERNEL_SAMPLES):
             step()
+            extra += 1
         torch.cuda.synchronize()
         env.sim.set_kernel_timing(0)
         tot_ms, launches = env.sim.read_kernel_timing()
-    kern_ms = tot_ms / max(launches, 1)
+        if launches == 0 and windowed:   # every window had another launch in it: time launches one by one
+            windowed = False
+            env.sim.set_kernel_timing(TIMING_PERIOD)
+            for _ in range(MIN_KERNEL_SAMPLES * TIMING_PERIOD):
+                step()
+            torch.cuda.synchronize()
+            env.sim.set_kernel_timing(0)
+            tot_ms, launches = env.sim.read_kernel_timing()
+        kern_ms = tot_ms / max(launches, 1)
     if rank != 0:
         if world > 1:
             torch.distributed.destroy_process_group()
         return
     value = N * args.steps * world / elapsed
-    bpe, breakdown = algorithmic_bytes_per_env_step(args.task, env)
-    kbpe = kernel_bytes_per_env(args.task, env)
-    # the committed PMC / SQ summaries profile the default workload of a task
-    # (flat ground, the cfg's solver, the foot-only model): other variants
-    # carry no traffic figure rather than another workload's
-    profiled = not (args.terrain or args.whole_body or args.solver_type is not None
-                    or args.contact_offset is not None)
-    traffic, traffic_src = committed_traffic(args.task, N) if profiled else (None, None)
-    achieved = bpe * N / (kern_ms * 1e-3) / 1e9
     sim_cfg = cfg["sim"]
     out = {
         "metric": "env-steps/sec (num_envs x step Hz)",
@@ -454,24 +492,34 @@ def main():
                  if rccl_world else None, "world_size": rccl_world or 1,
                  "collectives_in_timed_region": "barrier + max-over-ranks all_reduce of the elapsed time"
                  if rccl_world else None},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "kernel": "tg::step_par_kernel (one launch per simulate)", "kernel_ms": kern_ms,
-                     "kernel_launches": launches,
-                     "kernel_timing": (f"HIP events around windows of {TIMING_WINDOW} consecutive step-kernel "
-                                       "launches of the timed region" if windowed else
-                                       f"HIP events around every {TIMING_PERIOD}th launch of the timed region")
-                                      + (f" and of {extra} untimed steps after it" if extra else ""),
-                     "bytes_per_env_step": bpe, "bytes_source": "SURVEY.md §8(d) algorithmic bytes per env-step",
-                     "bytes_breakdown": breakdown, "algorithmic_bytes_per_launch": bpe * N,
-                     "kernel_bytes_per_env_step": kbpe,
-                     "traffic_over_algorithmic": traffic / (bpe * N) if traffic else None,
-                     "traffic_source": traffic_src},
     }
-    sq = committed_sq(args.task, N) if profiled else None
-    if sq is not None:
-        out["roofline"]["issue"] = sq
-    if not args.no_cpu_baseline and world == 1:
+    if args.full:
+        bpe, breakdown = algorithmic_bytes_per_env_step(args.task, env)
+        kbpe = kernel_bytes_per_env(args.task, env)
+        # the committed PMC / SQ summaries profile the default workload of a task
+        # (flat ground, the cfg's solver, the foot-only model): other variants
+        # carry no traffic figure rather than another workload's
+        profiled = not (args.terrain or args.whole_body or args.solver_type is not None
+                        or args.contact_offset is not None)
+        traffic, traffic_src = committed_traffic(args.task, N) if profiled else (None, None)
+        achieved = bpe * N / (kern_ms * 1e-3) / 1e9
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                           "kernel": "tg::step_par_kernel (one launch per simulate)", "kernel_ms": kern_ms,
+                           "kernel_launches": launches,
+                           "kernel_timing": (f"HIP events around windows of {TIMING_WINDOW} consecutive step-kernel "
+                                             "launches of the timed region" if windowed else
+                                             f"HIP events around every {TIMING_PERIOD}th launch of the timed region")
+                                            + (f" and of {extra} untimed steps after it" if extra else ""),
+                           "bytes_per_env_step": bpe, "bytes_source": "SURVEY.md §8(d) algorithmic bytes per env-step",
+                           "bytes_breakdown": breakdown, "algorithmic_bytes_per_launch": bpe * N,
+                           "kernel_bytes_per_env_step": kbpe,
+                           "traffic_over_algorithmic": traffic / (bpe * N) if traffic else None,
+                           "traffic_source": traffic_src}
+        sq = committed_sq(args.task, N) if profiled else None
+        if sq is not None:
+            out["roofline"]["issue"] = sq
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             info = host_cpu_info()
             thr = baseline_threads(info)

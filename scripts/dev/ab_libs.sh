@@ -14,7 +14,7 @@ for r in $(seq 1 $ROUNDS); do
   for t in $TASKS; do
     for kv in $LIBS; do
       n=${kv%%=*}; p=${kv#*=}
-      TG_LIB_PATH=$p timeout -k 10 200 python bench.py --task $t --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/${t}_${n}_$r.log 2>&1
+      TG_LIB_PATH=$p timeout -k 10 200 python bench.py --full --task $t --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/${t}_${n}_$r.log 2>&1
       rc=$?
       [ $rc -eq 0 ] || { echo "$t $n rc=$rc"; tail -5 $OUT/${t}_${n}_$r.log; exit $rc; }
       echo "$t $n r$r $(tail -c 4000 $OUT/${t}_${n}_$r.log | grep -o '"value": [0-9.e+]*\|"kernel_ms": [0-9.e+]*' | tr '\n' ' ')"

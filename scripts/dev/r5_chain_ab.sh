@@ -19,7 +19,7 @@ for r in 1 2; do
   for t in ThormangWalk Gogoro; do
     for v in chain:libtgsim.so list:libtgsim_list.so nosync:libtgsim_nosync.so; do
       n=${v%%:*}; lib=${v#*:}
-      TG_LIB_PATH=$L/$lib timeout -k 10 200 python bench.py --task $t --no-cpu-baseline > $OUT/${t}_${n}_r$r.log 2>&1 \
+      TG_LIB_PATH=$L/$lib timeout -k 10 200 python bench.py --full --task $t --no-cpu-baseline > $OUT/${t}_${n}_r$r.log 2>&1 \
         || { echo "$t $n failed"; tail -5 $OUT/${t}_${n}_r$r.log; exit 1; }
       echo "$t $n r$r $(tail -c 4000 $OUT/${t}_${n}_r$r.log | grep -o '"value": [0-9.e+]*\|"kernel_ms": [0-9.e+]*' | tr '\n' ' ')"
     done

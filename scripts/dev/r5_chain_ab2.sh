@@ -15,7 +15,7 @@ python scripts/dev/bitcmp_libs.py cmp $OUT/chain.npz $OUT/list.npz | tee $OUT/bi
 for r in 1 2; do
   for v in chain7:libtgsim.so list:libtgsim_list.so chain15:libtgsim_cm15.so; do
     n=${v%%:*}; lib=${v#*:}
-    TG_LIB_PATH=$L/$lib timeout -k 10 200 python bench.py --task ThormangWalk --no-cpu-baseline > $OUT/${n}_r$r.log 2>&1 \
+    TG_LIB_PATH=$L/$lib timeout -k 10 200 python bench.py --full --task ThormangWalk --no-cpu-baseline > $OUT/${n}_r$r.log 2>&1 \
       || { echo "$n failed"; tail -5 $OUT/${n}_r$r.log; exit 1; }
     echo "ThormangWalk $n r$r $(tail -c 4000 $OUT/${n}_r$r.log | grep -o '"value": [0-9.e+]*\|"kernel_ms": [0-9.e+]*' | tr '\n' ' ')"
   done

@@ -11,7 +11,7 @@ for r in 1 2; do
   for task in ThormangWalk Gogoro; do
     for v in cfg:"" off:"--contact-offset 0"; do
       n=${v%%:*}; opt=${v#*:}
-      timeout -k 10 200 python bench.py --task $task --no-cpu-baseline $opt > $OUT/${task}_${n}_r$r.log 2>&1 \
+      timeout -k 10 200 python bench.py --full --task $task --no-cpu-baseline $opt > $OUT/${task}_${n}_r$r.log 2>&1 \
         || { echo "$task $n failed"; tail -5 $OUT/${task}_${n}_r$r.log; exit 1; }
       echo "$task $n r$r $(tail -c 4000 $OUT/${task}_${n}_r$r.log | grep -o '"value": [0-9.e+]*\|"kernel_ms": [0-9.e+]*' | tr '\n' ' ')"
     done

@@ -12,7 +12,7 @@ OUT=${OUT:-gpurun_out/ghost}
 mkdir -p $OUT
 L=thormang_isaacgym_amd
 run() {  # name lib envs
-  TG_LIB_PATH=$L/$2 timeout -k 10 200 python bench.py --task ThormangWalk --num-envs $3 --no-cpu-baseline \
+  TG_LIB_PATH=$L/$2 timeout -k 10 200 python bench.py --full --task ThormangWalk --num-envs $3 --no-cpu-baseline \
     > $OUT/$1_$3_r$r.log 2>&1 || { echo "$1 $3 failed"; tail -5 $OUT/$1_$3_r$r.log; exit 1; }
   echo "$1 envs=$3 r$r $(tail -c 4000 $OUT/$1_$3_r$r.log | grep -o '"value": [0-9.e+]*\|"kernel_ms": [0-9.e+]*' | tr '\n' ' ')"
 }

@@ -13,7 +13,7 @@ for r in 1 2; do
   for v in base:libtgsim.so p1:libtgsim_probe1.so p2:libtgsim_probe2.so p4:libtgsim_probe4.so \
            p8:libtgsim_probe8.so p15:libtgsim_probe15.so; do
     n=${v%%:*}; lib=${v#*:}
-    TG_LIB_PATH=$L/$lib timeout -k 10 200 python bench.py --task ThormangWalk --no-cpu-baseline \
+    TG_LIB_PATH=$L/$lib timeout -k 10 200 python bench.py --full --task ThormangWalk --no-cpu-baseline \
       > $OUT/${n}_r$r.log 2>&1 || { echo "$n failed"; tail -5 $OUT/${n}_r$r.log; exit 1; }
     echo "$n r$r $(tail -c 4000 $OUT/${n}_r$r.log | grep -o '"value": [0-9.e+]*\|"kernel_ms": [0-9.e+]*' | tr '\n' ' ')"
   done

@@ -15,7 +15,7 @@ for r in 1 2; do
   for task in Gogoro GogoroPaper; do
     for v in main:libtgsim.so chs:libtgsim_chs.so; do
       n=${v%%:*}; lib=${v#*:}
-      TG_LIB_PATH=$L/$lib timeout -k 10 200 python bench.py --task $task --no-cpu-baseline > $OUT/${task}_${n}_r$r.log 2>&1 \
+      TG_LIB_PATH=$L/$lib timeout -k 10 200 python bench.py --full --task $task --no-cpu-baseline > $OUT/${task}_${n}_r$r.log 2>&1 \
         || { echo "$task $n failed"; tail -5 $OUT/${task}_${n}_r$r.log; exit 1; }
       echo "$task $n r$r $(tail -c 4000 $OUT/${task}_${n}_r$r.log | grep -o '"value": [0-9.e+]*\|"kernel_ms": [0-9.e+]*' | tr '\n' ' ')"
     done

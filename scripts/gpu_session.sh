@@ -23,11 +23,11 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   tail -1 $OUT/smoke.log
 fi
 if [ -z "${SKIP_BENCH:-}" ]; then
-timeout -k 10 400 python bench.py > $OUT/bench_default.log 2>&1 || exit $?
+timeout -k 10 400 python bench.py --full > $OUT/bench_default.log 2>&1 || exit $?
 tail -1 $OUT/bench_default.log | cut -c1-300
 run() {  # name, bench args...
   local n=$1; shift
-  timeout -k 10 300 python bench.py "$@" > $OUT/bench_$n.log 2>&1
+  timeout -k 10 300 python bench.py --full "$@" > $OUT/bench_$n.log 2>&1
   local rc=$?; echo "bench $n rc=$rc $(tail -c 3000 $OUT/bench_$n.log | grep -o '"value": [0-9.e+]*\|"ms_per_step": [0-9.e+]*\|"kernel_ms": [0-9.e+]*' | tr '\n' ' ')"
   [ $rc -eq 0 ] || exit $rc
 }

@@ -142,3 +142,38 @@ def test_bench_gpus_one_runs_in_process():
     r, lines = _bench(["--gpus", "1", "--steps", "3", "--warmup", "0"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert lines[0]["n_gpus"] == 1 and lines[0]["dist"]["world_size"] == 1
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: the step's return tuple as float32 <name>.npy; past
+    the byte limit every array keeps the same seeded sample of env rows, the
+    same rows on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    n = 64
+    obs = torch.arange(n * 3, dtype=torch.float32).reshape(n, 3)
+    result = ({"obs": obs, "states": obs[:, :2] * 2}, torch.arange(n, dtype=torch.float32),
+              torch.arange(n) % 2, {"time_outs": torch.arange(n) % 3 == 0})
+    bench.dump_outputs(str(tmp_path / "all"), result, rank=0, world=1)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["obs", "reset", "rew", "states", "time_outs"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["obs"], obs.numpy())
+    np.testing.assert_array_equal(got["reset"], (np.arange(n) % 2).astype(np.float32))
+    np.testing.assert_array_equal(got["time_outs"], (np.arange(n) % 3 == 0).astype(np.float32))
+    total = sum(a.nbytes for a in got.values())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", total // 4)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), result, rank=1, world=2)
+    s1 = {f: np.load(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")}
+    s2 = {f: np.load(tmp_path / "s2" / f) for f in os.listdir(tmp_path / "s2")}
+    assert sorted(s1) == [f"{k}_rank1.npy" for k in ("env_rows", "obs", "reset", "rew", "states", "time_outs")]
+    rows = s1["env_rows_rank1.npy"].astype(np.int64)
+    assert len(rows) == n // 4 and len(set(rows)) == len(rows) and (np.diff(rows) > 0).all()
+    assert sum(a.nbytes for k, a in s1.items() if not k.startswith("env_rows")) <= total // 4
+    np.testing.assert_array_equal(s1["obs_rank1.npy"], obs.numpy()[rows])
+    np.testing.assert_array_equal(s1["rew_rank1.npy"], rows.astype(np.float32))
+    for k in s1:
+        np.testing.assert_array_equal(s1[k], s2[k])

@@ -76,3 +76,42 @@ def test_gpu_bench_gpus_two_launches_two_ranks_on_one_gpu():
     print({k: d[k] for k in ("value", "n_gpus", "ms_per_step")}, d["dist"])
     assert d["n_gpus"] == 2 and d["dist"]["world_size"] == 2
     assert d["value"] > 0 and d["config"]["parallelism"] == "env-dp2"
+
+
+def test_gpu_bench_plain_line_dump_outputs_and_full(tmp_path):
+    """A plain `bench.py --steps K` line carries the headline (value,
+    ms_per_step, K timed steps) and neither the roofline block nor the CPU
+    baselines; `--full` adds the roofline block.  `--dump-outputs` writes the
+    last timed step's return as float32 arrays, identical between the two runs:
+    the inputs are fixed, and the dump is taken before the untimed steps
+    `--full` adds."""
+    _cuda()
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    out = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup",
+                            "5", "--num-envs", "1024", "--dump-outputs", str(tmp_path / name), *extra], env=env,
+                           cwd=repo, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out[name] = lines[0]
+    for d in out.values():
+        assert d["steps"] == 20 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 1024 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert "cpu_baseline" not in d
+    assert "roofline" not in out["plain"]
+    assert out["full"]["roofline"]["kernel_ms"] > 0 and out["full"]["roofline"]["kernel_launches"] >= 32
+    shapes = {"obs": (1024, 112), "rew": (1024,), "reset": (1024,), "time_outs": (1024,)}
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(f"{k}.npy" for k in shapes)
+    for k, shape in shapes.items():
+        a, b = np.load(tmp_path / "plain" / f"{k}.npy"), np.load(tmp_path / "full" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), k
+        np.testing.assert_array_equal(a, b, err_msg=k)
+    assert np.abs(np.load(tmp_path / "plain" / "obs.npy")).max() > 0

@@ -8,7 +8,6 @@ import ctypes as C
 import os
 
 import numpy as np
-import pytest
 
 from thormang_isaacgym_amd import abi
 from thormang_isaacgym_amd._lib import lib
@@ -18,7 +17,7 @@ from thormang_isaacgym_amd.model.urdf import load_urdf
 HERE = os.path.dirname(os.path.abspath(__file__))
 URDF = os.path.join(HERE, "golden", "urdf", "loader_tree.urdf")
 MESHES = os.path.join(HERE, "golden", "urdf")
-REF = "/root/reference/assets/urdf/gogoro"
+REF_ZIP = os.path.join(HERE, "golden", "urdf", "gogoro_assets.zip")   # the reference's two URDFs, the tyre mesh's vertices
 TG_ERR_MODEL = -3   # include/tgsim.h
 
 ARRAYS = [("link_parent", "num_links", 1, np.int32), ("link_group", "num_links", 1, np.int32),
@@ -208,13 +207,18 @@ def test_native_loader_bounds_the_link_chain_depth(tmp_path):
     assert rc == 0, msg
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference assets not present (build container only)")
-def test_native_loader_on_the_reference_assets():
+def test_native_loader_on_the_reference_assets(tmp_path):
     """The registered task's scooter with the reference's locked joints and the
-    tyre meshes (model/build_models.py), and the stand-alone Thormang URDF:
-    bit-identical arrays, hash and traits text.  (Named apart from the
-    compiled-in "gogoro", whose traits carry the fused task epilogue a
-    run-time model does not get.)"""
+    tyre meshes (model/build_models.py), and the stand-alone Thormang URDF,
+    unpacked from tests/golden/urdf/gogoro_assets.zip (of wheel_V3.obj the
+    vertex lines, all that either loader reads): bit-identical arrays, hash
+    and traits text.  (Named apart from the compiled-in "gogoro", whose traits
+    carry the fused task epilogue a run-time model does not get.)"""
+    import zipfile
     from thormang_isaacgym_amd.model.build_models import GOGORO_LOCKED
-    compare(f"{REF}/urdf/scooter_V13.urdf", locked=GOGORO_LOCKED, mesh_root=f"{REF}/meshes", name="scooter_v13")
-    compare(f"{REF}/urdf/thormang3.urdf", name="thormang_urdf")
+    with zipfile.ZipFile(REF_ZIP) as z:
+        z.extractall(tmp_path)
+    info, m, _ = compare(f"{tmp_path}/urdf/scooter_V13.urdf", locked=GOGORO_LOCKED, mesh_root=f"{tmp_path}/meshes",
+                         name="scooter_v13")
+    assert [s.kind for s in m.shapes].count("torus") == 2 and m.locked_dofs   # the tyres were fitted, the locks applied
+    compare(f"{tmp_path}/urdf/thormang3.urdf", name="thormang_urdf")
