@@ -39,6 +39,10 @@
  *                            (tasks/gogoro_realistic_turning_sim_paper.py:457)
  *   tg_apply_body_forces     the same, pre-reduced: one wrench per group [N,G,6]
  *   tg_simulate              gym.simulate (vec_task.py:335): sim.substeps substeps
+ *   tg_set_net_contact_force_tensor
+ *                            acquire_net_contact_force_tensor /
+ *                            refresh_net_contact_force_tensor
+ *                            (tasks/anymal.py:113,117)
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -243,6 +247,22 @@ int tg_set_sim_params(tg_sim *sim, const tg_sim_params *params);
  * linear velocity of the link's centre of mass (3, the root-state convention),
  * angular velocity (3); from the current root and dof state, stream-ordered. */
 int tg_rigid_body_states(tg_sim *sim, float *out);
+/* acquire_net_contact_force_tensor: out [N, L, 3] device, caller-owned, kept alive by the caller;
+ * NULL turns it off again.  Written in full by every later tg_simulate: entry
+ * (e, l) is the ground's force on link l of env e (links in model order, as
+ * tg_rigid_body_states), world frame, newtons, averaged over that call's
+ * substeps -- 1 / (substeps h) times the sum, over the substeps and over the
+ * normal and patch-friction rows of the link's shapes, of the row's
+ * stored-velocity multiplier times its direction.  Links without a collision
+ * shape read 0 (the call zero-fills out, stream-ordered); a simulate with 0
+ * substeps writes zeros.  As in IsaacGym the tensor holds the last simulate's
+ * forces until the next one; a reset does not clear it, and
+ * refresh_net_contact_force_tensor has nothing to do.  While the tensor is
+ * on, the task steps (tg_walk_step, tg_gogoro_step, tg_paper_step) run their
+ * post-physics as a separate launch after the last simulate; the results are
+ * those of that path.  Compiled-in models only: TG_ERR_MODEL for a model from
+ * tg_model_jit. */
+int tg_set_net_contact_force_tensor(tg_sim *sim, float *out);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

@@ -37,6 +37,14 @@ int launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t
     return rc == TG_OTHER_UNIT ? jit_launch_step(hash, a, stream, ev_begin, ev_end) : rc;
 }
 
+// the step with the net contact force export: compiled-in models only
+int launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
+                   hipEvent_t ev_end) {
+    int rc = unit_launch_step_cf(hash, a, cf, stream, ev_begin, ev_end);
+    if (rc == TG_OTHER_UNIT) rc = tree_launch_step_cf(hash, a, cf, stream, ev_begin, ev_end);
+    return rc == TG_OTHER_UNIT ? TG_ERR_MODEL : rc;
+}
+
 int launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
                        hipEvent_t ev_begin, hipEvent_t ev_end) {
     int rc = unit_launch_step_gogoro(hash, a, pa, stream, ev_begin, ev_end);

@@ -18,6 +18,10 @@ namespace tg {
 int tree_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
     return unit_launch_step(hash, a, stream, ev_begin, ev_end);
 }
+int tree_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
+                        hipEvent_t ev_end) {
+    return unit_launch_step_cf(hash, a, cf, stream, ev_begin, ev_end);
+}
 int tree_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
                             hipEvent_t ev_begin, hipEvent_t ev_end) {
     return unit_launch_step_gogoro(hash, a, pa, stream, ev_begin, ev_end);

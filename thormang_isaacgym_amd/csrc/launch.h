@@ -84,6 +84,27 @@ template <class M> int launch_model(const StepArgs &a, hipStream_t stream, hipEv
     }
 }
 
+// the step with the net contact force export (NoPostCF, cf [N, NL, 3]):
+// instantiated beside the plain pair for every model with contact rows; a
+// model without any has nothing to export and runs the plain kernel (the
+// tensor keeps the zeros it was enabled with)
+template <class M>
+int launch_model_cf(const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
+    if constexpr (!in_unit<M>()) {
+        return TG_OTHER_UNIT;
+    } else if constexpr (M::NROWS == 0) {
+        return launch_model<M>(a, stream, ev_begin, ev_end);
+    } else {
+        launch_compose<M>(a, stream);
+        if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
+        const NoPostCF::Args pa{cf};
+        if (int rc = a.hf ? launch_par<M, true, NoPostCF>(a, stream, pa) : launch_par<M, false, NoPostCF>(a, stream, pa))
+            return rc;
+        if (ev_end && hipEventRecord(ev_end, stream) != hipSuccess) return TG_ERR_HIP;
+        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
+    }
+}
+
 // the fused walk epilogue is instantiated for the lane-pair (humanoid-size)
 // trees on flat ground only
 template <class M>
@@ -154,6 +175,13 @@ static int unit_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream
     TG_FOR_EACH_MODEL(TG_U_LAUNCH)
     return TG_OTHER_UNIT;
 }
+#define TG_U_LAUNCH_CF(MODEL) \
+    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model_cf<MODEL>(a, cf, stream, ev_begin, ev_end);
+static int unit_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
+                               hipEvent_t ev_end) {
+    TG_FOR_EACH_MODEL(TG_U_LAUNCH_CF)
+    return TG_OTHER_UNIT;
+}
 static int unit_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
                                    hipEvent_t ev_begin, hipEvent_t ev_end) {
     TG_FOR_EACH_MODEL(TG_U_LAUNCH_GOGORO)
@@ -174,6 +202,8 @@ static int unit_launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPos
 
 // the humanoid unit's entries (articulation_tree.hip)
 int tree_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end);
+int tree_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
+                        hipEvent_t ev_end);
 int tree_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
                             hipEvent_t ev_begin, hipEvent_t ev_end);
 int tree_launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPostArgs &pa, hipStream_t stream,

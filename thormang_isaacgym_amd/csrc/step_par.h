@@ -600,6 +600,58 @@ struct NoPost {
     static constexpr bool T7_SYNC = false;  // publishes the term-7 block sum for an in-launch batch sum (PaperPost)
 };
 
+// NoPost that also exports the net contact force tensor
+// (tg_set_net_contact_force_tensor): cf [N, NL, 3], the ground's force on each
+// link in the world frame, averaged over the launch's substeps.  A policy
+// without a CF member exports nothing (PostCF), so every other instantiation
+// is compiled exactly as before.
+struct NoPostCF : NoPost {
+    struct Args {
+        float *cf;
+    };
+    static constexpr bool CF = true;
+};
+template <class P, class = void> struct PostCF {
+    static constexpr bool value = false;
+};
+template <class P> struct PostCF<P, decltype((void)P::CF)> {
+    static constexpr bool value = P::CF;
+};
+// the links that carry collision shapes (distinct entries of M::shape_link,
+// in shape order) and, per contact row, the index of its link in that list
+// (-1 for a torsion row: its Jacobian has no linear part, so no force)
+template <class M> struct CFLinks {
+    static constexpr int NSX = M::NS > 0 ? M::NS : 1, KX = M::NROWS > 0 ? M::NROWS : 1;
+    struct Tab {
+        int n;
+        int link[NSX];
+        int slot[KX];
+    };
+    static constexpr Tab make() {
+        Tab t{};
+        int base = 0;
+        for (int sh = 0; sh < M::NS; ++sh) {
+            int c = -1;
+            for (int k = 0; k < t.n; ++k)
+                if (t.link[k] == M::shape_link[sh]) c = k;
+            if (c < 0) {
+                c = t.n++;
+                t.link[c] = M::shape_link[sh];
+            }
+            const int nr = M::shape_nrows[sh], nf = nr == 1 ? 2 : 3;   // (shape_nfric)
+            for (int k = 0; k < nr + nf; ++k) t.slot[base + k] = k == nr + 2 ? -1 : c;
+            base += nr + nf;
+        }
+        return t;
+    }
+    static constexpr Tab tab = make();
+};
+// a lane's accumulators, 3 floats per link it owns
+template <int N> struct CFAcc {
+    float x[N] = {}, y[N] = {}, z[N] = {};
+};
+template <> struct CFAcc<0> {};
+
 // inverse of the group -> dof map: group of dof d, -1 for a locked dof
 template <class M> struct DofGroup {
     struct Arr {
@@ -1352,6 +1404,12 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
 #endif
     constexpr bool EPI_TOUCH = TG_EPI_TOUCH && P::TOUCH;
     float epi_touch = 0.f;
+    // net contact force export (NoPostCF): lane sub owns the shape-bearing
+    // links sub, sub + LPE, ... of CFLinks and sums their rows' world-frame
+    // impulses over the substeps in registers
+    constexpr bool CF = PostCF<P>::value && K > 0;
+    constexpr int NCF = CF ? (CFLinks<M>::tab.n + LPE - 1) / LPE : 0;
+    [[maybe_unused]] CFAcc<NCF> cfa;   // (no member without the export)
     for (int sub_i = 0; sub_i < a.substeps; ++sub_i) {
         // Passes 1-3 run with every position/velocity drive implicit and
         // unclamped; if some drive's implicit end-of-substep torque te - K*qdd
@@ -2899,6 +2957,28 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             }
             }
             TG_SYNC();
+            if constexpr (CF) {
+                // PL::LAM holds the stored-velocity multipliers of every sweep
+                // form now, and PL::ROW the rows' root-frame Jacobians as built
+                // (no variant writes PL::ROW after the rows' construction; the
+                // impulse application below only reads both).  R is still the
+                // orientation the substep started from
+#pragma unroll
+                for (int k = 0; k < NCF; ++k) {
+                    const int c = sub + k * LPE;
+                    V3 f = v3(0, 0, 0);
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        if (CFLinks<M>::tab.slot[j] < 0) continue;
+                        const float l = CFLinks<M>::tab.slot[j] == c ? s(PL::LAM + j) : 0.f;
+                        f = f + l * ldv3(s, PL::ROW + j * 8 + 3);
+                    }
+                    const V3 fw = mul(R, f);
+                    cfa.x[k] += fw.x;
+                    cfa.y[k] += fw.y;
+                    cfa.z[k] += fw.z;
+                }
+            }
 #ifdef TG_DUMP_ENV
             if (e == tg_dump_env && owner && lead && sub_i == tg_dump_sub) {
                 for (int i = 0; i < K; ++i) {
@@ -3187,6 +3267,24 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
         }
         TG_SYNC();
         TG_PROF(8)
+    }
+    if constexpr (CF) {
+        // mean force over the launch: the impulses' sum / (substeps * h);
+        // zeros when no substep ran.  One lane owns one link: plain stores
+        const float inv = a.substeps > 0 ? 1.0f / ((float)a.substeps * h) : 0.f;
+#pragma unroll
+        for (int k = 0; k < NCF; ++k) {
+            const int c = sub + k * LPE;
+            int link = CFLinks<M>::tab.link[0];   // (selected from the constant table, no load)
+#pragma unroll
+            for (int i = 1; i < CFLinks<M>::tab.n; ++i) link = c == i ? CFLinks<M>::tab.link[i] : link;
+            if (owner && c < CFLinks<M>::tab.n) {
+                float *o = pa.cf + ((size_t)e * M::NL + link) * 3;
+                o[0] = inv * cfa.x[k];
+                o[1] = inv * cfa.y[k];
+                o[2] = inv * cfa.z[k];
+            }
+        }
     }
     if constexpr (EPI_TOUCH) __asm__ volatile("" ::"v"(epi_touch));   // (keeps the touch load)
     if constexpr (P::on) {

@@ -73,6 +73,8 @@ struct tg_sim {
     float *root = nullptr, *dof = nullptr, *pos_tgt = nullptr, *vel_tgt = nullptr, *act = nullptr;
     float *props = nullptr, *force = nullptr, *mass_scale = nullptr, *shape_mu = nullptr, *comp = nullptr;
     float *zero_link3 = nullptr;   // [N*L*3] zeros (torque-only rigid-body force calls), lazily allocated
+    // net contact force tensor [N,L,3] (tg_set_net_contact_force_tensor), caller-owned; null: off
+    float *cf = nullptr;
     float *env_origin = nullptr;
     uint8_t *dirty = nullptr;
     int *err = nullptr;   // sticky state-error flag set by kernels (tg_sync reports it)
@@ -521,6 +523,9 @@ struct DeviceGuard {
 
 static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, const tg::WalkPostArgs *wp = nullptr,
                          const tg::GogoroPostArgs *gp = nullptr, const tg::PaperPostArgs *pp = nullptr) {
+    // the net contact force export has no fused-epilogue variant: the task
+    // steps take their general path (simulates, then the post-physics launch)
+    if (s->cf && (wp || gp || pp)) return 1;
     DeviceGuard dg(s->device);
     tg::StepArgs a = a_in;
     // the compose launch: every dirty env (host-side changes possible), the
@@ -589,7 +594,8 @@ static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, const tg::WalkPost
     int rc = wp   ? tg::launch_step_walk(s->hash, a, *wp, s->stream, ev.first, ev.second)
              : gp ? tg::launch_step_gogoro(s->hash, a, *gp, s->stream, ev.first, ev.second)
              : pp ? tg::launch_step_paper(s->hash, a, *pp, s->stream, ev.first, ev.second)
-                  : tg::launch_step(s->hash, a, s->stream, ev.first, ev.second);
+             : s->cf ? tg::launch_step_cf(s->hash, a, s->cf, s->stream, ev.first, ev.second)
+                     : tg::launch_step(s->hash, a, s->stream, ev.first, ev.second);
     // the pair joins the pending list only once both events were recorded by a
     // launch that went through; otherwise it goes back to the free list
     if (rc != 0) {
@@ -696,6 +702,24 @@ int tg_rigid_body_states(tg_sim *s, float *out) {
     win_touch(s);
     if (int rc = tg::launch_body_states(s->hash, s->root, s->dof, (int)s->N, out, s->stream))
         return fail(rc, "rigid-body state launch failed");
+    return TG_OK;
+}
+
+int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
+    if (int rc = check_sim(s)) return rc;
+    if (!out) {
+        s->cf = nullptr;
+        return TG_OK;
+    }
+    if (tg::jit_has(s->hash))
+        return fail(TG_ERR_MODEL,
+                    "tg_set_net_contact_force_tensor: the net contact force export exists for compiled-in models "
+                    "only, not for a model compiled at run time (tg_model_jit)");
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    // links without a shape are never written by the step kernel: they read 0
+    HIPCHK(hipMemsetAsync(out, 0, (size_t)s->N * s->L * 3 * sizeof(float), s->stream));
+    s->cf = out;
     return TG_OK;
 }
 

@@ -121,6 +121,17 @@ class NativeModel:
             self._h = None
 
 
+def contact_link_indices(model) -> list:
+    """The links of ``model`` (a ``Model`` or ``NativeModel``) that carry a
+    collision shape, ascending, as indices into ``model.links`` order: the
+    rows of the net contact force tensor that can be nonzero."""
+    if isinstance(model, NativeModel):
+        links = [int(model.desc.shape_link[i]) for i in range(model.num_shapes)]
+    else:
+        links = [model.link_index(s.link) for s in model.shapes]
+    return sorted(set(links))
+
+
 def _ptr(t: torch.Tensor | None):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -307,6 +318,27 @@ class Sim:
     def refresh_rigid_body_state_tensor(self):
         rb = self.acquire_rigid_body_state_tensor()
         check(lib().tg_rigid_body_states(self._h, _ptr(rb)), "refresh_rigid_body_state_tensor")
+
+    def acquire_net_contact_force_tensor(self) -> torch.Tensor:
+        """gym.acquire_net_contact_force_tensor (tasks/anymal.py:113): [N, L, 3]
+        live tensor, the ground's force on each link (world frame, newtons,
+        links in model order) averaged over the last simulate's substeps;
+        written by every simulate from now on.  Rows of links without a
+        collision shape stay 0 (``contact_link_indices`` lists the others).
+        Compiled-in models only; the task steps run unfused while it is on."""
+        if getattr(self, "net_contact_force", None) is None:
+            t = torch.zeros(self.num_envs, self.L, 3, dtype=torch.float32, device=self.device)
+            check(lib().tg_set_net_contact_force_tensor(self._h, _ptr(t)), "acquire_net_contact_force_tensor")
+            self.net_contact_force = t
+        return self.net_contact_force
+
+    def refresh_net_contact_force_tensor(self):
+        """gym.refresh_net_contact_force_tensor (tasks/anymal.py:117): the tensor
+        is written by simulate itself, nothing to do."""
+
+    @property
+    def contact_link_indices(self) -> list:
+        return contact_link_indices(self.model)
 
     def sync(self):
         check(lib().tg_sync(self._h), "sync")

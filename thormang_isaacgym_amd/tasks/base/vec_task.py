@@ -234,6 +234,15 @@ class VecTask(Env):
         self.sim.simulate()
         self.frame_count += 1
 
+    def acquire_net_contact_force_tensor(self) -> torch.Tensor:
+        """gym.acquire_net_contact_force_tensor (tasks/anymal.py:113): the sim's
+        live [N, L, 3] tensor of per-link ground forces (Sim)."""
+        return self.sim.acquire_net_contact_force_tensor()
+
+    def refresh_net_contact_force_tensor(self):
+        """gym.refresh_net_contact_force_tensor (tasks/anymal.py:117)."""
+        self.sim.refresh_net_contact_force_tensor()
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)

@@ -15,6 +15,12 @@ inertias scooter_V13.urdf carries and the xacro's foot boxes
 (model/build_models.py); ``env.asset.wholeBodyCollision: true`` adds the
 xacro's shin and hand boxes (model ``thormang_wb``).  Actions [N,33] in [-1,1] -> joint targets
 default + actionScale * a; observation [N,112] (tg_walk.h).
+
+``env.enableContactForces: true`` (optional, default false) acquires the net
+contact force tensor: ``contact_forces`` [N,L,3], ``feet_indices`` and
+``extras["feet_contact_force"]`` [N,2,3] after every step, for foot-contact
+terms a user adds; observation, reward and reset do not read them.  The step
+then runs its post-physics as a separate launch.
 """
 from __future__ import annotations
 
@@ -74,6 +80,14 @@ class ThormangWalk(VecTask):
         push_s = float(learn.get("pushInterval_s", 0.0))
         self.push_enabled = push_s > 0 and float(learn.get("pushForce", 0.0)) > 0
         self._bufs = self._make_buffers()
+        # env.enableContactForces: the per-link ground forces of the last
+        # simulate (legged tasks' foot-contact terms, tasks/anymal.py:113-117);
+        # observation, reward and reset do not use them
+        self.contact_forces = None
+        if bool(env.get("enableContactForces", False)):
+            self.contact_forces = self.acquire_net_contact_force_tensor()
+            self.feet_indices = torch.as_tensor(walk_feet_indices(self.model), dtype=torch.long, device=dev)
+            self._contact_extras()
         self.reset_idx(torch.arange(N, device=dev))
 
     # ------------------------------------------------------------ creation
@@ -145,6 +159,13 @@ class ThormangWalk(VecTask):
         check(lib().tg_walk_post_physics(self.sim.handle, C.byref(self.params), C.byref(self._bufs), _p(rd), _p(pd),
                                          self._counter()), "tg_walk_post_physics")
         self._keep_post = (rd, pd)
+        self._contact_extras()
+
+    def _contact_extras(self):
+        """extras["feet_contact_force"] [N, n_feet, 3]: the feet's rows of the
+        contact force tensor after this step (env.enableContactForces)."""
+        if self.contact_forces is not None:
+            self.extras["feet_contact_force"] = self.contact_forces[:, self.feet_indices].to(self.rl_device)
 
     def step(self, actions):
         if self.dr_randomizations.get("actions", None) or self.dr_randomizations.get("observations", None):
@@ -160,6 +181,7 @@ class ThormangWalk(VecTask):
         self.frame_count += self.control_freq_inv
         self._keep, self._keep_post = a, (rd, pd)
         self.extras["time_outs"] = self.timeout_buf
+        self._contact_extras()
         self.obs_dict["obs"] = self.obs_buf
         return self._rl_out()
 
@@ -180,6 +202,13 @@ def walk_model_name(cfg) -> str:
     ``env.asset.wholeBodyCollision`` ``thormang_wb`` (feet, shins and hands
     collide; model/build_models.py)."""
     return "thormang_wb" if cfg["env"].get("asset", {}).get("wholeBodyCollision", False) else "thormang"
+
+
+def walk_feet_indices(m) -> list:
+    """The foot links (l_leg_foot_link, r_leg_foot_link) among the links that
+    carry a collision shape, as indices into ``m.links``."""
+    from ..sim import contact_link_indices
+    return [i for i in contact_link_indices(m) if "foot" in m.links[i].name]
 
 
 def walk_asset_options(cfg) -> dict:
