@@ -26,11 +26,14 @@ import sys
 def kernels(path, flt):
     """{kernel: (code lines, descriptor lines)}; the function-local labels
     (.LBB<function index>_<block>) lose the index, which counts the unit's functions."""
-    code, desc, cur, mode = {}, {}, None, None
+    code, desc, cur, mode, funcs = {}, {}, None, None, set()
     for line in open(path):
         t = line.strip()
+        m = re.match(r"^\.type\s+(\w+),@function", t)
+        if m:   # (a data object's label, a model table with a mangled name, is no kernel)
+            funcs.add(m.group(1))
         m = re.match(r"^(\w+):\s*(;.*)?$", t)
-        if m and not t.startswith(".L") and mode is None and flt in m.group(1):
+        if m and m.group(1) in funcs and mode is None and flt in m.group(1):
             cur, mode = m.group(1), "code"
             code[cur] = []
             continue

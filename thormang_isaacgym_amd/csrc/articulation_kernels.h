@@ -1176,25 +1176,7 @@ struct WalkPost {
     static constexpr bool T7_SYNC = false;
     static constexpr int NPRE = 0;
     static constexpr bool PM_OUT = true;   // stores the pre-physics' actions / targets (pm_in_step) below
-    static constexpr bool TOUCH = true;
     using Args = WalkPostArgs;
-    // the line of the epilogue's inputs lane `sub` touches in the last
-    // substep (step_par.h EPI_TOUCH): progress, reset flag, last actions (two
-    // lines), commands, the reset root state; the other lanes the first
-    template <class M, int LPE>
-    static __device__ __forceinline__ const float *touch_addr(const Args &pa, const StepArgs &, int e, int sub) {
-        const tg_walk_buffers &b = pa.b;
-        constexpr int D = M::ND;
-        const float *la = b.last_actions + (size_t)e * D;
-        switch (sub) {
-        case 1: return reinterpret_cast<const float *>(b.reset_buf + e);
-        case 2: return la;
-        case 3: return la + (D - 1);
-        case 4: return b.commands + 3 * (size_t)e;
-        case 5: return b.root_reset + 13 * (size_t)e;
-        default: return reinterpret_cast<const float *>(b.progress_buf + e);
-        }
-    }
     static __device__ __forceinline__ float clampw(float x, float lo, float hi) {
         return x < lo ? lo : (x > hi ? hi : x);
     }
@@ -1507,7 +1489,6 @@ struct GogoroPost {
     static constexpr bool on = true;
     static constexpr bool T7_SYNC = false;
     static constexpr bool PM_OUT = false;
-    static constexpr bool TOUCH = false;
     using Args = GogoroPostArgs;
     // the translating-lock extension of an env the previous step reset (its
     // reset happens in this epilogue), LPE lanes x NPRE floats, loaded at
@@ -1983,13 +1964,9 @@ template <class M, int LN> struct RbLanes {
 // The same helpers (paper_math.h), Philox blocks and sum order as the post
 // kernel; this unit's transcendentals and the physics' fp contraction in the
 // link kinematics are the differences (tests/test_gpu_paper.py).
-#ifndef TG_PAPER_T7_END
-#define TG_PAPER_T7_END 1   // developer switch: 0 = reward term 7's batch sum before the histories (A/B)
-#endif
 struct PaperPost {
     static constexpr bool on = true;
     static constexpr bool PM_OUT = false;
-    static constexpr bool TOUCH = false;
     static constexpr bool T7_SYNC = true;
     using Args = PaperPostArgs;
     // the translating-lock extension of an env the previous step flagged for
@@ -2086,12 +2063,10 @@ struct PaperPost {
         }
         // reward term 7's batch sum (every workgroup's prologue published its block)
         // the term-7 arrival count, read with the first batch; the batch sum
-        // itself waits until the end (TG_PAPER_T7_END), where its loads overlap
+        // itself waits until the end of the epilogue, where its loads overlap
         // the epilogue's store drain
         const unsigned c0 = (threadIdx.x & 63) == 0 ? __hip_atomic_load(pa.t7_count, __ATOMIC_RELAXED,
                                                                        __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        double tot = 0.0;
-        if (!TG_PAPER_T7_END) tot = paper_t7_wait_sum(a.pp.t7, pa.t7_count, pa.t7_target, pa.nblk, a.err, c0);
         // ---- the extension and the draws to the env's LDS
         if constexpr (M::NTL > 0) {
 #pragma unroll
@@ -2189,7 +2164,6 @@ struct PaperPost {
             for (int k = 0; k < PO; ++k) last[k] = s(OB + k);
             rew = reward15(p, last);
             tilt = last[0];
-            if (!TG_PAPER_T7_END) finish_env(p, b, e, tot, tilt, prog, rew);
             commands(p, b, e, prog, L, last, draw(0, 5), draw(0, 6), draw(0, 7), draw(1, 7));
         }
         if (b.body_force && owner) {
@@ -2215,10 +2189,9 @@ struct PaperPost {
             rb.finish(b.root, b.dof_state, b.rb_forces, plink, e, pa.rb_out, sub, s.b, s.b + 9 * M::NG, b.dof_props,
                       p.num_envs, owner);
         }
-        if (TG_PAPER_T7_END) {   // reward term 7's batch sum, then the rewards / resets / time-outs
-            tot = paper_t7_wait_sum(a.pp.t7, pa.t7_count, pa.t7_target, pa.nblk, a.err, c0);
-            if (lead && owner) finish_env(p, b, e, tot, tilt, prog, rew);
-        }
+        // reward term 7's batch sum, then the rewards / resets / time-outs
+        const double tot = paper_t7_wait_sum(a.pp.t7, pa.t7_count, pa.t7_target, pa.nblk, a.err, c0);
+        if (lead && owner) finish_env(p, b, e, tot, tilt, prog, rew);
     }
 };
 

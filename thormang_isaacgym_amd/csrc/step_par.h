@@ -151,12 +151,6 @@ __device__ __forceinline__ int scr(int x) { return (x / 21) * GF + F_IA + x % 21
 __device__ __forceinline__ M3 ldR(const LE &s, int g) { return transpose(ldm3(s, g * GF + F_RT)); }
 __device__ __forceinline__ void stR(const LE &s, int g, const M3 &R) { stm3(s, g * GF + F_RT, transpose(R)); }
 
-// round 6: leaf groups' joint-space inertia from their local rigid inertia
-// (step_par_kernel d0l); 0 = pass 2b's root-origin form for every group (A/B)
-#ifndef TG_LEAF_D0
-#define TG_LEAF_D0 1
-#endif
-
 // per-group model table in LDS (ints; axis as float bits), built once per block
 enum : int { GI_PARENT = 0, GI_DOF = 1, GI_JT = 2, GI_NCH = 3, GI_CH = 4 };
 
@@ -203,16 +197,8 @@ template <class M> struct ParLayout {
     // unit-torque responses of up to WCM clamped drives.  Per env: G (the
     // responses' joint accelerations per group), R (root accelerations), A
     // (contact-group accelerations), J (row velocities, = J G), Minv
-#ifdef TG_NO_SUPER   // developer build: the bottom-up impulse application (A/B)
-    static constexpr bool SUPER = false;
-#else
     static constexpr bool SUPER = K > 0 && K * (M::MAXD + 6) <= M::NG * 21;
-#endif
-#ifdef TG_NO_WOOD   // developer build: the drive-clamp rerun instead (A/B)
-    static constexpr bool WOOD = false;
-#else
     static constexpr bool WOOD = M::NG <= 8 && M::NG - 1 <= M::LPE && (SUPER || K == 0);
-#endif
     static constexpr int WCM = 2;
     static constexpr int WB_G = (TOTAL0 + 3) & ~3;          // [WCM][8]
     static constexpr int WB_R = WB_G + WCM * 8;             // [WCM][6]
@@ -233,11 +219,7 @@ template <class M> struct ParLayout {
     // then 8-byte aligned and 16-byte moves become b64 pairs).  The scooters
     // keep 16-byte strides (2 mod 4 measured +1.9 % on 8 lanes per env and
     // +2.5 % / +1.5 % Gogoro / paper on lane pairs; profiles/r3/lds_*, ablations_r3)
-#ifdef TG_ES_PAD   // developer experiment: extra floats per env (LDS bank pattern)
-    static constexpr int ESPAD = TG_ES_PAD;
-#else
     static constexpr int ESPAD = M::NG >= 16 ? 2 : 0;
-#endif
     static constexpr int ES = ((TOTAL + 3) & ~3) + ESPAD;
     template <int EPB> static constexpr size_t bytes() { return ((size_t)EPB * ES + T_TOTAL) * 4; }
 };
@@ -264,7 +246,7 @@ template <class M> __device__ __forceinline__ GInfo ginfo(const int *gi, int g) 
     return GInfo{p[GI_PARENT], p[GI_DOF], p[GI_JT]};
 }
 
-// Chain schedule (round 5; TG_CHAIN, the lane-pair trees): one
+// Chain schedule (round 5; the lane-pair trees): one
 // schedule slot per root-to-leaf chain of the group tree -- slot s runs, at
 // step t, the group at depth t + 1 on the path from the root to its leaf --
 // so in every tree pass a group's parent (forward passes) or first child
@@ -279,32 +261,18 @@ template <class M> __device__ __forceinline__ GInfo ginfo(const int *gi, int g) 
 // the children's summation order (own + child 0 + child 1 + ...), so every
 // result is bit-identical to the list schedule's.  Leaves are the slots
 // (Thormang: 7 of 8), in depth-first order, children in child-list order.
-#ifndef TG_CHAIN
-#define TG_CHAIN 1   // developer switch: 0 = the list schedule for every tree (A/B)
-#endif
-// chain schedule: the forward passes have no LDS dependence between their
-// steps, pass 2b only where a group gathers another chain's head; 0 = a
-// wave-scope sync only there (and after each pass), 1 = after every step
-#ifndef TG_CHAIN_SYNC
-#define TG_CHAIN_SYNC 1
-#endif
-// the passes that use the chain registers (1 pass 1a, 2 pass 2b, 4 pass 3,
-// 8 the impulse top-down pass); the others run their list-schedule form over
-// the chain schedule (duplicates then load and store like owners: the same
-// values).  All four by default, bit-identical to the list schedule
-// (scripts/dev/r5_chain_mask.sh, scripts/dev/bitcmp_libs.py, profiles/r5/).
+// The forward passes have no LDS dependence between their steps, pass 2b only
+// where a group gathers another chain's head; every pass still syncs after
+// every step.  All four tree passes (pass 1a, pass 2b, pass 3, the impulse
+// top-down pass) use the chain registers, bit-identical to the list schedule
+// (scripts/dev/bitcmp_libs.py, profiles/r5/).
 // (The impulse pass stores the joint velocities from every lane of a group,
 // owners and duplicates alike: gating that store on ownership changed how the
 // compiler contracted the stored sum, and with it the rounding.)
-#ifndef TG_CHAIN_MASK
-#define TG_CHAIN_MASK 15
-#endif
-// every lane-pair tree with at least this many groups (the scooters' 6-group
+// On every lane-pair tree with at least this many groups (the scooters' 6-group
 // trees gain too: Gogoro 44.9 -> 43.3 us, GogoroPaper 36.6 -> 35.4 us,
 // bit-identical, profiles/r5/scooter_chain_ab.txt; 16 = the humanoids only)
-#ifndef TG_CHAIN_MIN_NG
-#define TG_CHAIN_MIN_NG 2
-#endif
+constexpr int CHAIN_MIN_NG = 2;
 
 template <class M> struct Chain {
     struct Tab {
@@ -347,7 +315,7 @@ template <class M> struct Chain {
         return x;
     }
     static constexpr Tab tab = make();
-    static constexpr bool ON = TG_CHAIN && M::PAIR && M::NG >= TG_CHAIN_MIN_NG && M::NG <= 128 && tab.nleaf <= M::SL &&
+    static constexpr bool ON = M::PAIR && M::NG >= CHAIN_MIN_NG && M::NG <= 128 && tab.nleaf <= M::SL &&
                                tab.depth <= M::NSTEP;
 };
 // the group (step t, slot) runs (chain: only its owner counts, for the gather widths)
@@ -390,9 +358,6 @@ template <class M> constexpr int step_smax(int t) {
         if (sched_own<M>(t, l) && M::nchild[sched_at<M>(t, l)] > m) m = M::nchild[sched_at<M>(t, l)];
     return m;
 }
-// pass 2b's step t gathers from LDS under the chain schedule (a group with
-// children after its first)
-template <class M> constexpr bool step_gathers(int t) { return step_smax<M>(t) >= 2; }
 template <class M> constexpr int max_nonroot_children() {
     int m = 0;
     for (int g = 1; g < M::NG; ++g) m = M::nchild[g] > m ? M::nchild[g] : m;
@@ -596,7 +561,6 @@ struct NoPost {
     static constexpr bool on = false;
     static constexpr int NPRE = 0;   // floats per lane an epilogue prefetches at kernel start
     static constexpr bool PM_OUT = false;   // the epilogue stores the walk pre-physics outputs itself
-    static constexpr bool TOUCH = false;    // touch_addr: a line of the epilogue's inputs per lane (below)
     static constexpr bool T7_SYNC = false;  // publishes the term-7 block sum for an in-launch batch sum (PaperPost)
 };
 
@@ -699,31 +663,8 @@ template <class M> __device__ __forceinline__ int dof_group(int d) {
     else return DofGroup<M>::tab.g[d];
 }
 
-// TG_ALIAS_DEV (developer timing experiment, wrong results): the lane-pair
-// trees' envs share TG_ALIAS_DEV LDS slots and the kernel is compiled for two
-// waves per SIMD, so two workgroups fit a CU -- what a per-env LDS footprint
-// half the size would buy
-// TG_GHOST_DEV (developer timing prototype, VERDICT r4 item 1, results
-// exact): the lane-pair trees run two envs per wavefront instead of four --
-// lanes 0-31 two real envs, lanes 32-63 their "ghost" twins, which compute
-// the same env on the same LDS slot and never store -- so 4096 envs are 2048
-// waves, and with half the LDS slots per workgroup and the kernel compiled
-// for two waves per SIMD two workgroups share a CU: two waves per SIMD, each
-// carrying the whole per-env chain for half the envs.  What a second wave
-// per SIMD buys when the env's work is NOT split across more lanes (the
-// 32-lane design's lower end)
-#if defined(TG_ALIAS_DEV)
-template <class M> constexpr int alias_slots(int epb) { return M::PAIR && TG_ALIAS_DEV < epb ? TG_ALIAS_DEV : epb; }
-#define TG_STEP_BOUNDS(M, EPB) __launch_bounds__(EPB * M::LPE, M::PAIR ? 2 : 1)
-#elif defined(TG_GHOST_DEV)
-template <class M> constexpr int alias_slots(int epb) { return (M::PAIR && M::NG >= 16) ? epb / 2 : epb; }
-#define TG_STEP_BOUNDS(M, EPB) __launch_bounds__(EPB * M::LPE, (M::PAIR && M::NG >= 16) ? 2 : 1)
-#else
-template <class M> constexpr int alias_slots(int epb) { return epb; }
-#define TG_STEP_BOUNDS(M, EPB) __launch_bounds__(EPB * M::LPE)
-#endif
 template <class M, int EPB, bool HF, class P = NoPost>
-__global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::Args pa) {
+__global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, typename P::Args pa) {
     constexpr int LPE = M::LPE;
     static_assert(64 % LPE == 0, "an env's lanes must share a wavefront");
     using CL = CompLayout<M>;
@@ -749,17 +690,13 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     auto swa = [](int j, int x) {
         return SW_SLOT ? (j < M::NG ? j * GF + F_IA + x : PL::SWX + 21 * (j - M::NG) + x) : scr(j * SW + x);
     };
-#ifdef TG_NO_SUPER
-    constexpr bool SUPER = false;
-#else
     constexpr bool SUPER = K > 0 && K * SW <= M::NG * 21;
-#endif
     constexpr bool SEPC = PL::SEPC;
     auto ia_c = [](int g) { return SEPC ? PL::CB + 32 * g : g * GF + F_IA; };        // pass-2 contribution I^a
     auto pa_c = [](int g) { return SEPC ? PL::CB + 32 * g + 24 : g * GF + F_PA; };   // pass-2 contribution p^a
     auto ac_s = [](int g) { return SEPC ? PL::CB + 32 * g : g * GF + F_PA; };        // pass-3 acceleration
     extern __shared__ __attribute__((aligned(16))) float lds_raw[];
-    int *tab = reinterpret_cast<int *>(lds_raw + alias_slots<M>(EPB) * PL::ES);
+    int *tab = reinterpret_cast<int *>(lds_raw + EPB * PL::ES);
     const int *gi = tab + PL::T_GI;
     const I4 *desc = reinterpret_cast<const I4 *>(tab + PL::T_DESC);   // [NSTEP][LPE]
     const float *zeros = reinterpret_cast<const float *>(tab + PL::T_ZERO);
@@ -778,18 +715,8 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     // of neighbouring chunks share 128-B lines)
     const int nb = gridDim.x;
     const int chunk = (nb % 8 == 0) ? (blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8 : blockIdx.x;
-#ifdef TG_GHOST_DEV
-    // (lanes 32-63 of a wave: the ghost twins of lanes 0-31's envs)
-    constexpr bool GH = M::PAIR && LPE == 16 && M::NG >= 16;
-    constexpr int EPR = GH ? EPB / 2 : EPB;   // real envs per workgroup
-    const int lr = GH ? (le >> 2) * 2 + (le & 1) : le;
-    const int e = min(chunk * EPR + lr, a.N - 1);
-    const bool owner = (!GH || (le & 3) < 2) && chunk * EPR + lr < a.N;
-#else
-    const int lr = le;
     const int e = min(chunk * EPB + le, a.N - 1);   // tail lanes redo the last env, never store
     const bool owner = chunk * EPB + le < a.N;
-#endif
     TG_PROF_INIT
 
     // the per-block tables, copied from the model's constants.  When every
@@ -802,18 +729,12 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     // group -> dof map, inside the table fill (OVL, round 4: its round trip
     // overlaps the table's; ThormangWalk -0.3 us, three A/B rounds,
     // profiles/r4/state_overlap_ab.txt)
-#ifndef TG_STATE_OVERLAP
-#define TG_STATE_OVERLAP 1   // developer switch: 0 = the state loads after the table barrier (A/B)
-#endif
-#ifndef TG_EARLY_STATE
-#define TG_EARLY_STATE 0   // developer switch: 1 = every tree with an affine group -> dof map
-#endif
     constexpr int NGR = (M::NG - 1 + LPE - 1) / LPE;
     // one-round trees: the env's state issued before the barrier (group ->
     // dof from the model's constants, not the LDS table) so its latency
     // overlaps the table fill's (larger trees: measured no gain, more live
     // registers across the barrier)
-    constexpr bool EARLY = NGR == 1 || (TG_EARLY_STATE && group_dof_offset<M>() != -1000);
+    constexpr bool EARLY = NGR == 1;
     float q0[NGR > 0 ? NGR : 1], qd0[NGR > 0 ? NGR : 1], rt0[13];
     const float *st_root = a.root + (size_t)e * 13;
     const float *st_dofs = a.dof + (size_t)e * a.D * 2;
@@ -822,7 +743,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                          M::NCG * M::MAXD <= NT && 32 <= NT;
     // (inside the one-pass table fill only: the whole-body model's 8-env
     // workgroups fill the table in loops and load the state after the barrier)
-    constexpr bool OVL = TG_STATE_OVERLAP && ONE && !EARLY && group_dof_offset<M>() != -1000;
+    constexpr bool OVL = ONE && !EARLY && group_dof_offset<M>() != -1000;
     if constexpr (ONE) {
         const int ig = tid < M::NG ? tid : 0, idd = tid < M::NSTEP * LPE ? tid : 0,
                   ipk = tid < PackTab<M>::NPW * LPE ? tid : 0, icp = tid < M::NCG * M::MAXD ? tid : 0;
@@ -879,15 +800,12 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     for (int i = tid; i < 32; i += EPB * LPE) tab[PL::T_ZERO + i] = 0;
     for (int i = tid; i < M::NCG * M::MAXD; i += EPB * LPE) tab[PL::T_CPATH + i] = M::cpath[i / M::MAXD][i % M::MAXD];
     }
-    const LE s{lds_raw + (lr % alias_slots<M>(EPB)) * PL::ES};
+    const LE s{lds_raw + le * PL::ES};
     const size_t N = a.N;
     const int D = a.D;
     const float h = a.h;
     const bool fix_base = a.fix_base != 0;
     const float *comp = a.comp;
-#ifdef TG_EXP_HOT   // developer experiment: every env reads env (e % 64)'s inputs (cache-resident)
-    const int ein = e % 64;
-#else
     // every env reads env 0's composite block while all blocks are equal
     // (a.cuni, uniform_check_kernel): one shared, cache-resident copy.  The
     // composites change only through a compose, which re-runs the check; the
@@ -895,7 +813,6 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     // zero-copy dof_props view takes effect at the next step as it does
     // without the shared cache
     const int ein = (a.cuni && *a.cuni) ? 0 : e;
-#endif
     // per-env inputs through 32-bit element offsets from the uniform base
     // pointers (scalar base + vector offset addressing, no 64-bit address math)
     const unsigned cbase = (unsigned)ein * M::KC;
@@ -988,11 +905,9 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     for (int w = 0; w < NPW; ++w) pkw[w] = tab[PL::T_PACK + w * LPE + sub];
     // step t's (group, parent, joint type) from the packed words (descriptor
     // fields x, y and z's joint type), or the LDS descriptor for NG > 128
-#ifndef TG_PACK_MASK
-#define TG_PACK_MASK 15   // passes using the packed words: 1 pass 1a, 2 pass 2b, 4 pass 3, 8 impulse top-down
-#endif
-    auto pdsc_on = [&](int t, auto PASS) {
-        if constexpr (PackTab<M>::ON && (TG_PACK_MASK & decltype(PASS)::value)) {
+    // (all four tree passes: pass 1a, pass 2b, pass 3, the impulse top-down pass)
+    auto pdsc_on = [&](int t) {
+        if constexpr (PackTab<M>::ON) {
             // (laundered through an empty volatile asm, which stays between the
             // wave barriers around it: the loads this step's fields address are
             // then issued where the pass issues them, a step or two ahead, not
@@ -1009,10 +924,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             return dsc(t);
         }
     };
-    auto pdsc = [&](int t) { return pdsc_on(t, IntC<1>{}); };
-    auto pdsc2 = [&](int t) { return pdsc_on(t, IntC<2>{}); };
-    auto pdsc3 = [&](int t) { return pdsc_on(t, IntC<4>{}); };
-    auto pdsc4 = [&](int t) { return pdsc_on(t, IntC<8>{}); };
+    auto pdsc = [&](int t) { return pdsc_on(t); };   // (the wrapper: load-bearing for code generation, the scooters' kernels)
     if constexpr ((M::FUSED & 4) != 0) {
         if (a.pp_in_step && a.pp.t7 && tid == 0) {
             if constexpr (P::T7_SYNC)
@@ -1125,11 +1037,6 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     };
     // pass 1b: groups sub, sub + LPE, ... of the env (all lanes, no schedule)
     constexpr int NR1 = (M::NG + LPE - 1) / LPE;
-#ifdef TG_DEV_R2   // developer timing probe (results wrong): the all-groups passes stop after two rounds
-    constexpr int NRX = NR1 < 2 ? NR1 : 2;
-#else
-    constexpr int NRX = NR1;
-#endif
     auto load_inertia = [&](float (*x)[12]) {   // mass, com, inertia (10 + 2 pad) of the lane's groups
 #pragma unroll
         for (int r = 0; r < NR1; ++r) {
@@ -1203,10 +1110,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     // one-round trees: every schedule step's joint placement too (constant
     // over the launch: the epilogue's in-place seat moves come after the last
     // substep), so pass 1a waits for them once per launch, not once per substep
-#ifndef TG_KIN_ONCE
-#define TG_KIN_ONCE 1   // developer switch: 0 = per-substep prefetch ring (A/B)
-#endif
-    constexpr bool KIN1 = NR1 == 1 && TG_KIN_ONCE;
+    constexpr bool KIN1 = NR1 == 1;
     float kin1[KIN1 ? M::NSTEP : 1][12];
     if constexpr (KIN1) {
 #pragma unroll
@@ -1217,21 +1121,15 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
     // loaded once here instead of inside every substep's contact setup, where
     // the loads sat on the chain (Gogoro 45.4 -> 45.1 us, GogoroPaper 36.9 ->
     // 36.5 us, A/B twice)
-#ifndef TG_SHAPE_ONCE
-#define TG_SHAPE_ONCE 1   // developer switch: 0 = loads inside the contact setup (A/B)
-#endif
     // one lane per contact ROW when every row has a lane (ROWPAR, round 4;
     // the contact setup below), else one lane per shape; either way the
     // lane's shape is loaded here
-#ifndef TG_ROW_PAR
-#define TG_ROW_PAR 1   // developer switch: 0 = one lane per shape builds its rows (A/B)
-#endif
     // (multi-point patches only -- the box faces' 7 rows per shape: on the
     // scooters' one-point tori, 3 rows per shape, every lane redoing the
     // shape geometry measured +0.35 % (Gogoro), where Thormang gains 1.0 %,
     // profiles/r4/rowpar_ab.txt)
-    constexpr bool ROWPAR = TG_ROW_PAR && M::NS > 0 && PL::K <= LPE && max_shape_rows<M>() > 1;
-    constexpr bool SHP1 = TG_SHAPE_ONCE && M::NS > 0 && (ROWPAR || M::NS <= LPE);
+    constexpr bool ROWPAR = M::NS > 0 && PL::K <= LPE && max_shape_rows<M>() > 1;
+    constexpr bool SHP1 = M::NS > 0 && (ROWPAR || M::NS <= LPE);
     float shp1[SHP1 ? 12 : 1], smu1 = 0.f;
     if constexpr (SHP1) {
         const int sh = ROWPAR ? row_shape_sel<M>(sub < PL::K ? sub : 0) : (sub < M::NS ? sub : 0);
@@ -1399,11 +1297,6 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             return false;
         }
     };
-#ifndef TG_EPI_TOUCH
-#define TG_EPI_TOUCH 0   // developer switch: 1 = touch the epilogue's inputs in the last substep (round 4 A/B: +0.6 us, AGPRs 54 -> 65; profiles/r4/epilogue_touch_ab.txt)
-#endif
-    constexpr bool EPI_TOUCH = TG_EPI_TOUCH && P::TOUCH;
-    float epi_touch = 0.f;
     // net contact force export (NoPostCF): lane sub owns the shape-bearing
     // links sub, sub + LPE, ... of CFLinks and sums their rows' world-frame
     // impulses over the substeps in registers
@@ -1471,16 +1364,9 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
         }
         if (lead) stsv(s, F_V, v0);
         TG_SYNC();
-#ifndef TG_PROBE
-#define TG_PROBE 0   // developer timing probes (results wrong): the tree passes' parent / child LDS traffic
-#endif               // replaced by the lane's own previous-step registers (1 pass 1a, 2 pass 2b, 4 pass 3, 8 impulse)
         // (chain schedule: the parent's pose and velocity are the lane's own
         // previous step's, the root's at step 0)
-        constexpr bool CH = Chain<M>::ON && (TG_CHAIN_MASK & 1);
-        constexpr bool CH1 = CH || (TG_PROBE & 1);
-#ifndef TG_Q_AHEAD
-#define TG_Q_AHEAD 1   // pass 1a: q, qd loaded two steps ahead (0: in the step, the A/B control)
-#endif
+        constexpr bool CH = Chain<M>::ON;
         M3 pr_R = eye3();
         V3 pr_P = v3(0, 0, 0);
         SV pr_v = v0;
@@ -1491,27 +1377,22 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             qq[0] = s(o + F_Q);
             qq[1] = s(o + F_QD);
         };
-        // chain form without branches (TG_1A_FLAT): every lane runs its step,
+        // chain form without branches (FLAT1): every lane runs its step,
         // idle lanes on the root's inputs, and a lane that does not own its
         // group stores into the Delassus / row area, which the contact setup
         // rebuilds later in the substep -- straight-line code, so the
         // compiler can overlap a step's parent-independent work (sin / cos,
         // the joint rotation) with the previous step's chain
-#ifndef TG_1A_FLAT
-#define TG_1A_FLAT 1
-#endif
-        constexpr bool FLAT1 = CH && TG_1A_FLAT && PL::VFREE - PL::W >= F_V + 6;
+        constexpr bool FLAT1 = CH && PL::VFREE - PL::W >= F_V + 6;
 // an idle lane (its chain ended) updates its chain registers too -- they
 // are dead after the pass -- so the update is a register rename, not a
-// divergent branch of 18 moves: on trees of at least TG_1A_IDLE_FREE groups
+// divergent branch of 18 moves: on trees of at least IDLE_FREE_MIN_NG groups
 // (the humanoids: ThormangWalk 49.4 -> 48.1 us, bit-identical,
 // profiles/r5/idle_free_ab.txt).  The scooters keep the branch: without it
 // the compiler fuses some multiply-adds differently (fp-contract works per
 // basic block), which changes their rounding (1e-4 after 100 steps).
-#ifndef TG_1A_IDLE_FREE
-#define TG_1A_IDLE_FREE 16
-#endif
-        constexpr bool IDLE_FREE = TG_1A_IDLE_FREE > 0 && M::NG >= TG_1A_IDLE_FREE;
+        constexpr int IDLE_FREE_MIN_NG = 16;
+        constexpr bool IDLE_FREE = M::NG >= IDLE_FREE_MIN_NG;
         auto body1f = [&](const I4 &dc, const float *ck, const float *qq) {
             const int g = dc.x, jt = d_jt(dc);
             const float qg = qq[0], qdg = qq[1];
@@ -1539,7 +1420,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             stm3(s, os + F_RT, transpose(Rg));
             stv3(s, os + F_P, Pg);
             stsv(s, os + F_V, vg);
-            if (IDLE_FREE || g > 0) {   // (see TG_1A_IDLE_FREE)
+            if (IDLE_FREE || g > 0) {   // (see IDLE_FREE_MIN_NG)
                 pr_R = Rg;
                 pr_P = Pg;
                 pr_v = vg;
@@ -1556,7 +1437,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                 M3 Rp;
                 V3 Pp;
                 SV vp;
-                if constexpr (CH1) {
+                if constexpr (CH) {
                     Rp = pr_R;
                     Pp = pr_P;
                     vp = pr_v;
@@ -1565,12 +1446,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                     Pp = ldv3(s, par * GF + F_P);
                     vp = ldsv(s, par * GF + F_V);
                 }
-#if TG_Q_AHEAD
                 const float qg = qq[0], qdg = qq[1];
-#else
-                (void)qq;
-                const float qg = s(o + F_Q), qdg = s(o + F_QD);
-#endif
                 M3 Rpc;   // child -> parent rotation at q, then the root-frame pose
 #pragma unroll
                 for (int k = 0; k < 9; ++k) Rpc.a[k] = ck[k];
@@ -1596,135 +1472,74 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                     stv3(s, o + F_P, Pg);
                     stsv(s, o + F_V, vg);
                 }
-                if constexpr (CH1) {
+                if constexpr (CH) {
                     pr_R = Rg;
                     pr_P = Pg;
                     pr_v = vg;
                 }
             }
-            if constexpr (!CH || TG_CHAIN_SYNC) TG_SYNC();
+            TG_SYNC();
         };
-        static_assert(!FLAT1 || TG_Q_AHEAD, "the flat chain form takes q, qd from the prefetch ring");
         // fully unrolled, inputs two steps ahead in a 3-deep ring (renamed
         // registers, no copies: the wait for step t's inputs leaves steps
         // t + 1 and t + 2 in flight)
         float qr[3][2];
-#ifndef TG_1A_REPS
-#define TG_1A_REPS 1   // developer ablation: pass 1a run this many times (idempotent: its marginal cost)
-#endif
 #pragma unroll 1
-        for (int rep1 = 0; rep1 < TG_1A_REPS; ++rep1) {
-        if (rep1 > 0) {
-            pr_R = eye3();
-            pr_P = v3(0, 0, 0);
-            pr_v = v0;
-        }
+        for (int once = 0; once < 1; ++once) {   // (one trip: load-bearing for code generation, the scooters' kernels)
         if constexpr (KIN1) {
             I4 dr[3];
             dr[0] = pdsc(0);
-            if (TG_Q_AHEAD) ld_q(dr[0], qr[0]);
+            ld_q(dr[0], qr[0]);
             if constexpr (M::NSTEP > 1) {
                 dr[1] = pdsc(1);
-                if (TG_Q_AHEAD) ld_q(dr[1], qr[1]);
+                ld_q(dr[1], qr[1]);
             }
 #pragma unroll
             for (int t = 0; t < M::NSTEP; ++t) {
                 if (t + 2 < M::NSTEP) {
                     dr[(t + 2) % 3] = pdsc(t + 2);
-                    if (TG_Q_AHEAD) ld_q(dr[(t + 2) % 3], qr[(t + 2) % 3]);
+                    ld_q(dr[(t + 2) % 3], qr[(t + 2) % 3]);
                 }
                 body1(dr[t % 3], kin1[t], qr[t % 3]);
             }
         } else {
-#ifndef TG_KIN_AHEAD
-#define TG_KIN_AHEAD 2   // pass 1a: the joint placements (composite cache) issued this many steps ahead
-#endif
-        constexpr int KA = TG_KIN_AHEAD, KR = KA + 1;
+        // the joint placements (composite cache) issued this many steps ahead
+        constexpr int KIN_AHEAD = 2;
+        constexpr int KA = KIN_AHEAD, KR = KA + 1;
         float kr[KR][12], qk[KR][2];
         I4 dr[KR];
 #pragma unroll
         for (int t = 0; t < KA && t < M::NSTEP; ++t) {
             dr[t] = pdsc(t);
             load_kin(dr[t].x, kr[t]);
-            if (TG_Q_AHEAD) ld_q(dr[t], qk[t]);
+            ld_q(dr[t], qk[t]);
         }
 #pragma unroll
         for (int t = 0; t < M::NSTEP; ++t) {
             if (t + KA < M::NSTEP) {
                 dr[(t + KA) % KR] = pdsc(t + KA);
                 load_kin(dr[(t + KA) % KR].x, kr[(t + KA) % KR]);
-                if (TG_Q_AHEAD) ld_q(dr[(t + KA) % KR], qk[(t + KA) % KR]);
+                ld_q(dr[(t + KA) % KR], qk[(t + KA) % KR]);
             }
             body1(dr[t % KR], kr[t % KR], qk[t % KR]);
         }
         }
         }
-        if constexpr (CH && (!TG_CHAIN_SYNC || FLAT1)) TG_SYNC();   // (pass 1b reads every group's pose)
-#ifdef TG_DUMMY_STEPS
-        // developer ablation: TG_DUMMY_STEPS dependent LDS round trips with no
-        // arithmetic (kind 0: one float; kind 1: pass 1a's traffic, 18 floats
-        // read from the next lane's slot, 18 written to the own slot) in the
-        // (not yet used) Delassus / row area: the fixed cost of a schedule step
-        {
-            float *ds = s.b + PL::W;
-            for (int t = 0; t < TG_DUMMY_STEPS; ++t) {
-                const float *src = ds + 20 * ((sub + 1) % LPE);
-                float *dst = ds + 20 * sub;
-#if TG_DUMMY_KIND == 0
-                float x = src[0];
-                __asm__ volatile("" : "+v"(x));
-                dst[0] = x;
-#elif TG_DUMMY_KIND == 2   // 18 read, 1 written
-                float x[18];
-#pragma unroll
-                for (int k = 0; k < 18; ++k) x[k] = src[k];
-#pragma unroll
-                for (int k = 0; k < 18; ++k) __asm__ volatile("" : "+v"(x[k]));
-                dst[0] = x[0];
-#elif TG_DUMMY_KIND == 3   // 1 read, 18 written
-                float x = src[0];
-                __asm__ volatile("" : "+v"(x));
-#pragma unroll
-                for (int k = 0; k < 18; ++k) dst[k] = x;
-#elif TG_DUMMY_KIND == 4   // kind 1, stores by one lane of each pair only
-                float x[18];
-#pragma unroll
-                for (int k = 0; k < 18; ++k) x[k] = src[k];
-#pragma unroll
-                for (int k = 0; k < 18; ++k) __asm__ volatile("" : "+v"(x[k]));
-                if (sub < M::SL) {
-#pragma unroll
-                    for (int k = 0; k < 18; ++k) dst[k] = x[k];
-                }
-#else
-                float x[18];
-#pragma unroll
-                for (int k = 0; k < 18; ++k) x[k] = src[k];
-#pragma unroll
-                for (int k = 0; k < 18; ++k) __asm__ volatile("" : "+v"(x[k]));
-#pragma unroll
-                for (int k = 0; k < 18; ++k) dst[k] = x[k];
-#endif
-                TG_SYNC();
-            }
-        }
-#endif
+        if constexpr (FLAT1) TG_SYNC();   // (pass 1b reads every group's pose)
 #ifdef TG_PROF_SPLIT0   // developer: pass 1a of the first substep into its own slot (20)
         TG_PROF(sub_i == 0 ? 20 : 16)
 #else
         TG_PROF(16)
 #endif
 #pragma unroll
-        for (int r = 0; r < NRX; ++r) {
+        for (int r = 0; r < NR1; ++r) {
             const int g = sub + r * LPE;
             if (g < M::NG) body_bias(g, ldsv(s, g * GF + F_V), ldR(s, g), ldv3(s, g * GF + F_P), gr, cin[r]);
-            if constexpr (TG_LEAF_D0) {
-                const int gl = min(g, M::NG - 1);
-                const bool leaf = g > 0 && g < M::NG && gi[gl * GIW + GI_NCH] == 0;
-                const bool rev = all_revolute<M>() || gi[gl * GIW + GI_JT] == TG_JOINT_REVOLUTE;
-                const float *ci = cin[r];
-                d0l[r] = leaf ? (rev ? ci[6] + ci[0] * (ci[1] * ci[1] + ci[2] * ci[2]) : ci[0]) : -1.f;
-            }
+            const int gl = min(g, M::NG - 1);
+            const bool leaf = g > 0 && g < M::NG && gi[gl * GIW + GI_NCH] == 0;
+            const bool rev = all_revolute<M>() || gi[gl * GIW + GI_JT] == TG_JOINT_REVOLUTE;
+            const float *ci = cin[r];
+            d0l[r] = leaf ? (rev ? ci[6] + ci[0] * (ci[1] * ci[1] + ci[2] * ci[2]) : ci[0]) : -1.f;
         }
         TG_SYNC();
         }   // pass 1
@@ -1742,19 +1557,13 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
         // only the stores predicated, so the compiler cannot sink a load into a
         // conditional block that uses it: the rounds share one memory latency.
         float cdr[NR1][10];
-        if constexpr (EPI_TOUCH) {
-            // the last substep: one line of the epilogue's inputs per lane
-            // brought into the cache with this pass's own HBM loads, so the
-            // epilogue's loads at the end of the kernel hit it
-            if (sub_i == a.substeps - 1 && cp == 0) epi_touch = *P::template touch_addr<M, LPE>(pa, a, e, sub);
-        }
 #pragma unroll
         for (int r = 0; r < NR1; ++r) {
             const int gc = min(max(sub + r * LPE, 1), M::NG - 1);
             load_drv(bounded(gi[gc * GIW + GI_DOF], 0, 1 << 16), cdr[r]);
         }
 #pragma unroll
-        for (int r = 0; r < NRX; ++r) {
+        for (int r = 0; r < NR1; ++r) {
             const int g0 = sub + r * LPE;
             const bool valid = g0 > 0 && g0 < M::NG;
             const int g = min(max(g0, 1), M::NG - 1);
@@ -1797,7 +1606,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                 }
                 if (!SEPC || cp == 0) stsv(s, o + F_V, cbv);
                 // (a leaf: D and u complete here from its local D0, pass 2b adds 0 x D0)
-                const bool lf = TG_LEAF_D0 && d0l[r] >= 0.f;
+                const bool lf = d0l[r] >= 0.f;
                 s(o + F_DINV) = (1.f + be) * cd[0] + Dimp + (lf ? (1.f + be) * d0l[r] : 0.f);
                 s(o + F_UU) = tau + al * cd[0] + (lf ? al * d0l[r] : 0.f);
                 s(o + F_QDS) = lf ? 0.f : al;
@@ -1858,7 +1667,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                 // was not rerun and F_V already holds cb
                 if (!SEPC || cp == 0) stsv(s, o + F_V, crm(ldsv(s, o + F_V), qd * ldSm<M>(s, g, bounded(gi[g * GIW + GI_JT], 0, 4))));
                 // (a leaf: D and u complete here from its local D0, pass 2b adds 0 x D0)
-                const bool lf = TG_LEAF_D0 && d0l[r] >= 0.f;
+                const bool lf = d0l[r] >= 0.f;
                 s(o + F_DINV) = (1.f + be) * cd[0] + Dimp + (lf ? (1.f + be) * d0l[r] : 0.f);
                 s(o + F_UU) = tau + al * cd[0] + (lf ? al * d0l[r] : 0.f);
                 s(o + F_QDS) = lf ? 0.f : al;
@@ -1894,12 +1703,12 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             constexpr int t = M::NSTEP - 1 - decltype(TT)::value;
             const I4 dc = dnext;   // (children for the gather)
             if constexpr (t > 0) dnext = dsc(t - 1);
-            const I4 pc = pdsc2(t);  // own group from registers: its loads need not wait for dc
+            const I4 pc = pdsc(t);  // own group from registers: its loads need not wait for dc
             const int g = pc.x;
             // (chain schedule: each group on its owner lane only; the first
             // child's contribution is in this lane's registers from the step
             // before, zeros for a leaf)
-            constexpr bool CH2 = Chain<M>::ON && (TG_CHAIN_MASK & 2);
+            constexpr bool CH2 = Chain<M>::ON;
             if (g > 0 && (!CH2 || d_own(pc))) {
                 const int o = g * GF;
                 float X[6], Bm[9], ph[3], cb1[3], cb2[3];
@@ -1942,7 +1751,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                     }
                 };
                 constexpr int smax = step_smax<M>(t);
-                if constexpr (CH2 || (TG_PROBE & 2)) {
+                if constexpr (CH2) {
                     // the first child from registers, then the children after it
                     // (other chains' heads) from LDS -- the list schedule's order;
                     // a leaf adds nothing (not even the zeros its registers hold:
@@ -2002,7 +1811,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                 // schedule: into this lane's registers for the parent (B in its
                 // canonical orientation: half 1 holds its transpose, bitwise),
                 // and to LDS only when the parent is another lane's or the root
-                if constexpr (CH2 || (TG_PROBE & 2)) {
+                if constexpr (CH2) {
 #pragma unroll
                     for (int k = 0; k < 6; ++k) p2X[k] = X[k];
 #pragma unroll
@@ -2011,7 +1820,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                         for (int j = 0; j < 3; ++j) p2B[3 * i + j] = hb ? Y[3 * j + i] : Y[3 * i + j];
                     p2p[0] = pav.x; p2p[1] = pav.y; p2p[2] = pav.z;
                 }
-                if (!(CH2 || (TG_PROBE & 2)) || (CH2 && d_store(dc))) {
+                if (!CH2 || d_store(dc)) {
 #pragma unroll
                     for (int k = 0; k < 6; ++k) s(ia_c(g) + 15 * hh + k) = X[k];
                     if (!hb) {
@@ -2021,10 +1830,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                     stv3(s, pa_c(g) + 3 * hh, pav);
                 }
             }
-            // (chain schedule: a sync where the next step gathers another chain's
-            // head, and after the last step -- the root gathers its children)
-            if constexpr (!CH2 || TG_CHAIN_SYNC || t == 0) TG_SYNC();
-            else if constexpr (step_gathers<M>(t - 1)) TG_SYNC();
+            TG_SYNC();
         });
         } else {
         // unrolled (round 2: Gogoro 8.27e7 -> 8.36e7, GogoroPaper 8.55e7 -> 8.64e7, A/B twice)
@@ -2034,7 +1840,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             constexpr int t = M::NSTEP - 1 - decltype(TT)::value;
             const I4 dc = dnext;   // (children for the gather)
             if constexpr (t > 0) dnext = dsc(t - 1);
-            const I4 pc = pdsc2(t);
+            const I4 pc = pdsc(t);
             const int g = pc.x;
             if (g > 0) {
                 const int o = g * GF;
@@ -2106,7 +1912,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
         Own ow[2];
         SV pr3 = a0;
         (void)pr3;
-        dr[0] = pdsc3(0);
+        dr[0] = pdsc(0);
         ow[0] = ld_own(dr[0]);
 #pragma unroll
         for (int t = 0; t < M::NSTEP; ++t) {
@@ -2114,12 +1920,12 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             const Own &w = ow[t % 2];
             const int g = dc.x;
             // (chain schedule: the parent's acceleration is the lane's previous step's)
-            constexpr bool CH3 = (Chain<M>::ON && (TG_CHAIN_MASK & 4)) || (TG_PROBE & 4);
+            constexpr bool CH3 = Chain<M>::ON;
             SV apar;
             if constexpr (CH3) apar = pr3;
             else apar = ldsv(s, ac_s(max(dc.y, 0)));
             if (t + 1 < M::NSTEP) {
-                dr[(t + 1) % 2] = pdsc3(t + 1);
+                dr[(t + 1) % 2] = pdsc(t + 1);
                 ow[(t + 1) % 2] = ld_own(dr[(t + 1) % 2]);
             }
             if (g > 0) {
@@ -2140,9 +1946,8 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                     }
                 }
             }
-            if constexpr (!(Chain<M>::ON && (TG_CHAIN_MASK & 4)) || TG_CHAIN_SYNC) TG_SYNC();
+            TG_SYNC();
         }
-        if constexpr (Chain<M>::ON && (TG_CHAIN_MASK & 4) && !TG_CHAIN_SYNC) TG_SYNC();   // (the flag and F_QDS are read below)
         }
         if constexpr (PL::WOOD) {
             if (cp == 0 && s(PL::FLG) != 0.f && wood_update()) break;   // else the rerun below
@@ -2723,23 +2528,9 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
 #pragma unroll
                     for (int jj = 0; jj < JL; ++jj) rv[jj] += wr[jj][i] * d;
                 };
-#ifdef TG_PGS_REFRESH   // developer build (drift study): row velocities re-formed at every sweep
-                float vfr[JL];
-#pragma unroll
-                for (int jj = 0; jj < JL; ++jj) vfr[jj] = rv[jj];
-#endif
                 auto sweeps = [&](int n_it, auto SUBC) {
 #pragma unroll 1
                 for (int it = 0; it < n_it; ++it) {
-#ifdef TG_PGS_REFRESH
-#pragma unroll
-                    for (int jj = 0; jj < JL; ++jj) {
-                        float r = vfr[jj];
-#pragma unroll
-                        for (int c = 0; c < K; ++c) r += wr[jj][c] * lam[c];
-                        rv[jj] = r;
-                    }
-#endif
 #pragma unroll
                     for (int sh = 0; sh < M::NS; ++sh) {
                         const int rb = row_base<M>(sh), nr = M::shape_nrows[sh];
@@ -3055,7 +2846,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                 OwnI ow[2];
                 SV pri = da0, priv = da0v;
                 (void)pri; (void)priv;
-                dr[0] = pdsc4(0);
+                dr[0] = pdsc(0);
                 ow[0] = ld_own(dr[0]);
 #pragma unroll
                 for (int t = 0; t < M::NSTEP; ++t) {
@@ -3064,7 +2855,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                     const int g = dc.x;
                     const int op = max(dc.y, 0) * GF;
                     // (chain schedule: the parent's responses are the lane's previous step's)
-                    constexpr bool CHI = (Chain<M>::ON && (TG_CHAIN_MASK & 8)) || (TG_PROBE & 8);
+                    constexpr bool CHI = Chain<M>::ON;
                     SV ap, av;
                     if constexpr (CHI) {
                         ap = pri;
@@ -3075,7 +2866,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                         av = vit ? ldsv(s, op + F_V) : sv0();
                     }
                     if (t + 1 < M::NSTEP) {
-                        dr[(t + 1) % 2] = pdsc4(t + 1);
+                        dr[(t + 1) % 2] = pdsc(t + 1);
                         ow[(t + 1) % 2] = ld_own(dr[(t + 1) % 2]);
                     }
                     if (g > 0) {
@@ -3097,9 +2888,8 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                             s(o + F_QD) = w.qds + xv;
                         }
                     }
-                    if constexpr (!(Chain<M>::ON && (TG_CHAIN_MASK & 8)) || TG_CHAIN_SYNC) TG_SYNC();
+                    TG_SYNC();
                 }
-                if constexpr (Chain<M>::ON && (TG_CHAIN_MASK & 8) && !TG_CHAIN_SYNC) TG_SYNC();
             } else {
                 // bottom-up gather, root solve, top-down -- once per multiplier
                 // set: with velocity iterations first the bias-free one (its
@@ -3219,7 +3009,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
         // (F_QD, v0v) when velocity iterations ran
         const bool vst = M::NS > 0 && (a.viters > 0 || a.tgs);
 #pragma unroll
-        for (int r = 0; r < NRX; ++r) {
+        for (int r = 0; r < NR1; ++r) {
             const int g = 1 + sub + r * LPE;
             if (g >= M::NG) break;
             const int o = g * GF;
@@ -3245,11 +3035,7 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
                 // error is a large relative error in the orientation increment,
                 // the largest GPU-specific term of the Gogoro drift study
                 // (profiles/r3/drift_gogoro.txt); once per substep
-#ifdef TG_FAST_QUAT   // developer build: the hardware approximation (drift study control)
-                __sincosf(0.5f * an, &sa, &ca);
-#else
                 sincosf(0.5f * an, &sa, &ca);
-#endif
                 const float kk = sa / wn;
                 dx = v0.w.x * kk; dy = v0.w.y * kk; dz = v0.w.z * kk; dw = ca;
             }
@@ -3286,7 +3072,6 @@ __global__ TG_STEP_BOUNDS(M, EPB) void step_par_kernel(StepArgs a, typename P::A
             }
         }
     }
-    if constexpr (EPI_TOUCH) __asm__ volatile("" ::"v"(epi_touch));   // (keeps the touch load)
     if constexpr (P::on) {
         // final root state in the world frame (every lane of the env holds it)
         const V3 wwo = mul(R, v0.w);

@@ -155,11 +155,8 @@ __device__ void walk_env(const tg_walk_params &p, const tg_walk_buffers &b, int 
     b.timeout_buf[e] = (prog >= p.max_episode_length - 1) && rs;
 }
 
-#ifndef TG_WALK_POST_WPB
-#define TG_WALK_POST_WPB 16
-#endif
 // WALK_POST_WPB wavefronts (envs) per workgroup
-constexpr int WALK_POST_WPB = TG_WALK_POST_WPB;
+constexpr int WALK_POST_WPB = 16;
 __global__ __launch_bounds__(64 * WALK_POST_WPB) void walk_post_kernel(tg_walk_params p, tg_walk_buffers b,
                                                                        const float *reset_draws, const float *push_draws,
                                                                        uint32_t c_lo, uint32_t c_hi) {
