@@ -43,6 +43,9 @@
  *                            acquire_net_contact_force_tensor /
  *                            refresh_net_contact_force_tensor
  *                            (tasks/anymal.py:113,117)
+ *   tg_set_dof_force_tensor  acquire_dof_force_tensor / refresh_dof_force_tensor
+ *                            (tasks/MA_OP3.py:91,96), with
+ *                            enable_actor_dof_force_sensors (:275) implied
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -263,6 +266,35 @@ int tg_rigid_body_states(tg_sim *sim, float *out);
  * those of that path.  Compiled-in models only: TG_ERR_MODEL for a model from
  * tg_model_jit. */
 int tg_set_net_contact_force_tensor(tg_sim *sim, float *out);
+/* acquire_dof_force_tensor: out [N, D] device, caller-owned, kept alive by the
+ * caller; NULL turns it off again.  Written in full by every later
+ * tg_simulate: entry (e, d) is the actuator's generalised force on DOF d of
+ * env e (N m for a revolute joint, N for a prismatic one), the mean over that
+ * call's substeps of the substep value tau.  With qd0 the DOF velocity at the
+ * substep's start, qd1 the STORED velocity at its end (the bias-free one when
+ * velocity iterations or TGS run, after the velocity limit -- the convention
+ * of the contact tensor's multipliers) and h the substep:
+ *   - POS or VEL drive, implicit in the substep's final solve:
+ *       tau = te - K (qd1 - qd0) / h,
+ *       te = kp (q* - q0 - h qd0) + kd (qd* - qd0),  K = h kd + h^2 kp,
+ *     the implicit PD law at the end-of-substep velocity, so it includes the
+ *     drive's reaction to the contact impulses;
+ *   - POS or VEL drive that the effort clamp made explicit (by the Woodbury
+ *     update or by the rerun): exactly +effort or -effort, the value the solve
+ *     used;
+ *   - EFFORT mode: clamp(actuation, +-effort) when an actuation tensor is
+ *     set, else 0;
+ *   - NONE mode and locked DOFs: 0.
+ * The joint-limit spring and damper are NOT part of tau: it is the actuator's
+ * force, which is what a torque penalty or a power estimate wants.  A
+ * simulate with 0 substeps writes zeros.  As in IsaacGym the tensor holds the
+ * last simulate's values until the next one; a reset does not clear it, and
+ * refresh_dof_force_tensor has nothing to do.  It works together with the net
+ * contact force tensor.  While the tensor is on, the task steps (tg_walk_step,
+ * tg_gogoro_step, tg_paper_step) run their post-physics as a separate launch
+ * after the last simulate; the results are those of that path.  Compiled-in
+ * models only: TG_ERR_MODEL for a model from tg_model_jit. */
+int tg_set_dof_force_tensor(tg_sim *sim, float *out);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

@@ -45,6 +45,15 @@ int launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stre
     return rc == TG_OTHER_UNIT ? TG_ERR_MODEL : rc;
 }
 
+// the step with the DOF force export (and the contact one when cf is set):
+// compiled-in models only
+int launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream, hipEvent_t ev_begin,
+                   hipEvent_t ev_end) {
+    int rc = unit_launch_step_df(hash, a, cf, df, stream, ev_begin, ev_end);
+    if (rc == TG_OTHER_UNIT) rc = tree_launch_step_df(hash, a, cf, df, stream, ev_begin, ev_end);
+    return rc == TG_OTHER_UNIT ? TG_ERR_MODEL : rc;
+}
+
 int launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
                        hipEvent_t ev_begin, hipEvent_t ev_end) {
     int rc = unit_launch_step_gogoro(hash, a, pa, stream, ev_begin, ev_end);

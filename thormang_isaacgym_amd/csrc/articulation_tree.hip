@@ -22,6 +22,10 @@ int tree_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t
                         hipEvent_t ev_end) {
     return unit_launch_step_cf(hash, a, cf, stream, ev_begin, ev_end);
 }
+int tree_launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream,
+                        hipEvent_t ev_begin, hipEvent_t ev_end) {
+    return unit_launch_step_df(hash, a, cf, df, stream, ev_begin, ev_end);
+}
 int tree_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
                             hipEvent_t ev_begin, hipEvent_t ev_end) {
     return unit_launch_step_gogoro(hash, a, pa, stream, ev_begin, ev_end);

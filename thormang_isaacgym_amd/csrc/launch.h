@@ -95,6 +95,25 @@ int launch_model_cf(const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t
     }
 }
 
+// the step with the DOF force export (NoPostDF, df [N, ND]) and, when cf is
+// not null, the net contact force export too: one more pair per model, with
+// or without contact rows (a model without any has no contact part)
+template <class M>
+int launch_model_df(const StepArgs &a, float *cf, float *df, hipStream_t stream, hipEvent_t ev_begin,
+                    hipEvent_t ev_end) {
+    if constexpr (!in_unit<M>()) {
+        return TG_OTHER_UNIT;
+    } else {
+        launch_compose<M>(a, stream);
+        if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
+        const NoPostDF::Args pa{cf, df};
+        if (int rc = a.hf ? launch_par<M, true, NoPostDF>(a, stream, pa) : launch_par<M, false, NoPostDF>(a, stream, pa))
+            return rc;
+        if (ev_end && hipEventRecord(ev_end, stream) != hipSuccess) return TG_ERR_HIP;
+        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
+    }
+}
+
 // the fused walk epilogue is instantiated for the lane-pair (humanoid-size)
 // trees on flat ground only
 template <class M>
@@ -172,6 +191,13 @@ static int unit_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipS
     TG_FOR_EACH_MODEL(TG_U_LAUNCH_CF)
     return TG_OTHER_UNIT;
 }
+#define TG_U_LAUNCH_DF(MODEL) \
+    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model_df<MODEL>(a, cf, df, stream, ev_begin, ev_end);
+static int unit_launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream,
+                               hipEvent_t ev_begin, hipEvent_t ev_end) {
+    TG_FOR_EACH_MODEL(TG_U_LAUNCH_DF)
+    return TG_OTHER_UNIT;
+}
 static int unit_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
                                    hipEvent_t ev_begin, hipEvent_t ev_end) {
     TG_FOR_EACH_MODEL(TG_U_LAUNCH_GOGORO)
@@ -194,6 +220,8 @@ static int unit_launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPos
 int tree_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end);
 int tree_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
                         hipEvent_t ev_end);
+int tree_launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream,
+                        hipEvent_t ev_begin, hipEvent_t ev_end);
 int tree_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
                             hipEvent_t ev_begin, hipEvent_t ev_end);
 int tree_launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPostArgs &pa, hipStream_t stream,

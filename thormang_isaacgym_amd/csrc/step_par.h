@@ -616,6 +616,33 @@ template <int N> struct CFAcc {
 };
 template <> struct CFAcc<0> {};
 
+// NoPost that exports the DOF force tensor (tg_set_dof_force_tensor): df
+// [N, ND], the actuator's generalised force on each DOF, averaged over the
+// launch's substeps.  The one policy also carries the net contact force
+// pointer, so that both tensors can be on together: a null cf skips the contact
+// stores, and a model without contact rows has no contact part at all.  A
+// policy without a DF member exports nothing (PostDF), so every other
+// instantiation is compiled exactly as before.
+struct NoPostDF : NoPost {
+    struct Args {
+        float *cf;
+        float *df;
+    };
+    static constexpr bool CF = true;
+    static constexpr bool DF = true;
+};
+template <class P, class = void> struct PostDF {
+    static constexpr bool value = false;
+};
+template <class P> struct PostDF<P, decltype((void)P::DF)> {
+    static constexpr bool value = P::DF;
+};
+// a lane's accumulators, one float per group it owns at the integration
+template <int N> struct DFAcc {
+    float v[N] = {};
+};
+template <> struct DFAcc<0> {};
+
 // inverse of the group -> dof map: group of dof d, -1 for a locked dof
 template <class M> struct DofGroup {
     struct Arr {
@@ -1303,6 +1330,15 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
     constexpr bool CF = PostCF<P>::value && K > 0;
     constexpr int NCF = CF ? (CFLinks<M>::tab.n + LPE - 1) / LPE : 0;
     [[maybe_unused]] CFAcc<NCF> cfa;   // (no member without the export)
+    // DOF force export (NoPostDF): lane sub owns the groups 1 + sub, 1 + sub +
+    // LPE, ... (the integration's assignment) and sums their substep torques
+    // tau = te - K (qd1 - qd0) / h in registers.  The F_CL slots carry (te, K)
+    // to the end of the substep -- nothing after the clamp pass writes them --
+    // with a clamped drive as (+-effort, 0), an effort-mode DOF as (its
+    // clamped actuation, -1), and qd0 in the effort's slot once the clamp
+    // pass is over
+    constexpr bool DF = PostDF<P>::value;
+    [[maybe_unused]] DFAcc<DF ? NR1 : 0> dfa;
     for (int sub_i = 0; sub_i < a.substeps; ++sub_i) {
         // Passes 1-3 run with every position/velocity drive implicit and
         // unclamped; if some drive's implicit end-of-substep torque te - K*qdd
@@ -1604,6 +1640,15 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
                     s(o + F_CL + 1) = cl1;
                     s(o + F_CL + 2) = eff;
                 }
+                if constexpr (DF) {
+                    // the export's (te, K): an effort-mode torque once, and the
+                    // rerun's clamp decision, which F_UU no longer shows later
+                    if (cp == 0 && !drv) s(o + F_CL) = ef;
+                    if (clampd) {
+                        s(o + F_CL) = tau;
+                        s(o + F_CL + 1) = 0.f;
+                    }
+                }
                 if (!SEPC || cp == 0) stsv(s, o + F_V, cbv);
                 // (a leaf: D and u complete here from its local D0, pass 2b adds 0 x D0)
                 const bool lf = d0l[r] >= 0.f;
@@ -1626,6 +1671,7 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
                 const float kp = cd[2], kd = cd[3];
                 const float eff = cd[4];
                 float cl0 = 0.f, cl1 = -1.f;   // clamp scratch (te, K) of the first solve
+                [[maybe_unused]] bool dfx = false;   // (DF) tau is the explicit torque: effort mode, or clamped
                 if (mode == TG_DOF_MODE_POS || mode == TG_DOF_MODE_VEL) {
                     const float te = kp * (cd[7] - q - h * qd) + kd * (cd[8] - qd);
                     const float K = h * kd + h * h * kp;
@@ -1640,8 +1686,10 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
                         }
                     }
                     if (implicit) { tau += te; Dimp += K; }
+                    if constexpr (DF) dfx = !implicit;
                 } else {
                     if (mode == TG_DOF_MODE_EFFORT && a.act) tau += fminf(fmaxf(cd[9], -eff), eff);
+                    if constexpr (DF) dfx = cp == 0;
                 }
                 // limit spring + damping (kl = lim_k D0 / h^2, cl = lim_c D0 / h),
                 // damping/implicit terms ramped in past the limit
@@ -1661,6 +1709,14 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
                     s(o + F_CL) = cl0;
                     s(o + F_CL + 1) = cl1;
                     s(o + F_CL + 2) = eff;
+                }
+                if constexpr (DF) {
+                    // the export's (te, K): an effort-mode torque once (K stays
+                    // -1), and the rerun's clamp decision as (+-effort, 0)
+                    if (dfx) {
+                        s(o + F_CL) = tau;
+                        if (cp == 1) s(o + F_CL + 1) = 0.f;
+                    }
                 }
                 // with D0 = S.I^A.S + armature: D = (1 + be) D0 + Dimp, tau + al D0
                 // cb replaces v (dead after pass 1b) in F_V; on a SEPC rerun pass 1
@@ -1954,6 +2010,28 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
         }
         if (cp == 0 && s(PL::FLG) == 0.f) break;
         }   // clamp pass
+        if constexpr (DF) {
+            // every reader of the clamp scratch is done (pass 3 and the Woodbury
+            // update end on a barrier).  A drive the Woodbury update clamped
+            // (wn > 0: the update went through, and F_C1 still holds the sides
+            // pass 3 wrote -- the contact sweeps reuse the slot only later)
+            // becomes (+-effort, 0) like the rerun's; the effort's slot then
+            // takes qd0, which the velocity iterations overwrite in F_QD
+#pragma unroll
+            for (int r = 0; r < NR1; ++r) {
+                const int g = 1 + sub + r * LPE;
+                if (g >= M::NG) break;
+                const int o = g * GF;
+                if constexpr (PL::WOOD) {
+                    const float sg = s(o + F_C1), eff = s(o + F_CL + 2);
+                    if (wn > 0 && sg != 0.f) {
+                        s(o + F_CL) = sg > 0.f ? eff : -eff;
+                        s(o + F_CL + 1) = 0.f;
+                    }
+                }
+                s(o + F_CL + 2) = s(o + F_QD);
+            }
+        }
         SV v0s = v0 + h * a0;
         v0s.v = v0s.v + h * cross(v0.w, v0.v);
         if (fix_base) v0s = sv0();
@@ -3019,6 +3097,9 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
                 x = fminf(fmaxf(x, -vl), vl);
                 xv = fminf(fmaxf(xv, -vl), vl);
             }
+            // (DF) the implicit drive law at the stored end-of-substep velocity;
+            // K <= 0 marks an explicit torque (clamped, effort mode, none)
+            if constexpr (DF) dfa.v[r] += s(o + F_CL) - fmaxf(s(o + F_CL + 1), 0.f) * ((xv - s(o + F_CL + 2)) / h);
             s(o + F_QD) = xv;
             s(o + F_Q) += h * x;
         }
@@ -3064,12 +3145,31 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
             int link = CFLinks<M>::tab.link[0];   // (selected from the constant table, no load)
 #pragma unroll
             for (int i = 1; i < CFLinks<M>::tab.n; ++i) link = c == i ? CFLinks<M>::tab.link[i] : link;
-            if (owner && c < CFLinks<M>::tab.n) {
+            if (owner && c < CFLinks<M>::tab.n && (!DF || pa.cf)) {   // (NoPostDF: the contact tensor may be off)
                 float *o = pa.cf + ((size_t)e * M::NL + link) * 3;
                 o[0] = inv * cfa.x[k];
                 o[1] = inv * cfa.y[k];
                 o[2] = inv * cfa.z[k];
             }
+        }
+    }
+    if constexpr (DF) {
+        // mean actuator force over the launch (zeros when no substep ran):
+        // one lane owns one group, hence one DOF -- plain stores; the locked
+        // DOFs read 0, so the tensor is rewritten in full
+        const float inv = a.substeps > 0 ? 1.0f / (float)a.substeps : 0.f;
+        if (owner) {
+            float *o = pa.df + (size_t)e * M::ND;
+#pragma unroll
+            for (int r = 0; r < NR1; ++r) {
+                const int g = 1 + sub + r * LPE;
+                if (g < M::NG) {
+                    const int d = bounded(gi[g * GIW + GI_DOF], 0, 1 << 16);
+                    if (d < M::ND) o[d] = inv * dfa.v[r];
+                }
+            }
+            for (int d = sub; d < M::ND; d += LPE)
+                if (M::dof_locked[d]) o[d] = 0.f;
         }
     }
     if constexpr (P::on) {

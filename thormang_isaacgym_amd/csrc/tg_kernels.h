@@ -173,6 +173,11 @@ int launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t
 // models only (TG_ERR_MODEL otherwise)
 int launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin = nullptr,
                    hipEvent_t ev_end = nullptr);
+// launch_step with the DOF force export (step_par.h NoPostDF): df [N, D] is
+// written in full; cf as in launch_step_cf, or null for no contact export.
+// Compiled-in models only (TG_ERR_MODEL otherwise)
+int launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream,
+                   hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 int compiled_hashes(uint64_t *out, int cap);
 int launch_body_states(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)

@@ -75,6 +75,8 @@ struct tg_sim {
     float *zero_link3 = nullptr;   // [N*L*3] zeros (torque-only rigid-body force calls), lazily allocated
     // net contact force tensor [N,L,3] (tg_set_net_contact_force_tensor), caller-owned; null: off
     float *cf = nullptr;
+    // DOF force tensor [N,D] (tg_set_dof_force_tensor), caller-owned; null: off
+    float *df = nullptr;
     float *env_origin = nullptr;
     uint8_t *dirty = nullptr;
     int *err = nullptr;   // sticky state-error flag set by kernels (tg_sync reports it)
@@ -523,9 +525,10 @@ struct DeviceGuard {
 
 static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, const tg::WalkPostArgs *wp = nullptr,
                          const tg::GogoroPostArgs *gp = nullptr, const tg::PaperPostArgs *pp = nullptr) {
-    // the net contact force export has no fused-epilogue variant: the task
-    // steps take their general path (simulates, then the post-physics launch)
-    if (s->cf && (wp || gp || pp)) return 1;
+    // the net contact force and DOF force exports have no fused-epilogue
+    // variant: the task steps take their general path (simulates, then the
+    // post-physics launch)
+    if ((s->cf || s->df) && (wp || gp || pp)) return 1;
     DeviceGuard dg(s->device);
     tg::StepArgs a = a_in;
     // the compose launch: every dirty env (host-side changes possible), the
@@ -594,6 +597,7 @@ static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, const tg::WalkPost
     int rc = wp   ? tg::launch_step_walk(s->hash, a, *wp, s->stream, ev.first, ev.second)
              : gp ? tg::launch_step_gogoro(s->hash, a, *gp, s->stream, ev.first, ev.second)
              : pp ? tg::launch_step_paper(s->hash, a, *pp, s->stream, ev.first, ev.second)
+             : s->df ? tg::launch_step_df(s->hash, a, s->cf, s->df, s->stream, ev.first, ev.second)
              : s->cf ? tg::launch_step_cf(s->hash, a, s->cf, s->stream, ev.first, ev.second)
                      : tg::launch_step(s->hash, a, s->stream, ev.first, ev.second);
     // the pair joins the pending list only once both events were recorded by a
@@ -720,6 +724,25 @@ int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
     // links without a shape are never written by the step kernel: they read 0
     HIPCHK(hipMemsetAsync(out, 0, (size_t)s->N * s->L * 3 * sizeof(float), s->stream));
     s->cf = out;
+    return TG_OK;
+}
+
+int tg_set_dof_force_tensor(tg_sim *s, float *out) {
+    if (int rc = check_sim(s)) return rc;
+    if (!out) {
+        s->df = nullptr;
+        return TG_OK;
+    }
+    if (tg::jit_has(s->hash))
+        return fail(TG_ERR_MODEL,
+                    "tg_set_dof_force_tensor: the DOF force export exists for compiled-in models only, not for a "
+                    "model compiled at run time (tg_model_jit)");
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    // (the step kernel rewrites every entry, the locked DOFs' zeros included;
+    // until the first simulate the tensor reads 0)
+    HIPCHK(hipMemsetAsync(out, 0, (size_t)s->N * s->D * sizeof(float), s->stream));
+    s->df = out;
     return TG_OK;
 }
 

@@ -336,6 +336,25 @@ class Sim:
         """gym.refresh_net_contact_force_tensor (tasks/anymal.py:117): the tensor
         is written by simulate itself, nothing to do."""
 
+    def acquire_dof_force_tensor(self) -> torch.Tensor:
+        """gym.acquire_dof_force_tensor (tasks/MA_OP3.py:91): [N, D] live tensor,
+        the actuator's force on each DOF (N m revolute, N prismatic) averaged
+        over the last simulate's substeps: the implicit PD law at the stored
+        end-of-substep velocity, +-effort where the clamp acted, the clamped
+        actuation in effort mode, 0 for undriven and locked DOFs (tgsim.h);
+        written by every simulate from now on.  No per-actor
+        enable_actor_dof_force_sensors is needed.  Compiled-in models only;
+        the task steps run unfused while it is on."""
+        if getattr(self, "dof_force", None) is None:
+            t = torch.zeros(self.num_envs, self.D, dtype=torch.float32, device=self.device)
+            check(lib().tg_set_dof_force_tensor(self._h, _ptr(t)), "acquire_dof_force_tensor")
+            self.dof_force = t
+        return self.dof_force
+
+    def refresh_dof_force_tensor(self):
+        """gym.refresh_dof_force_tensor (tasks/MA_OP3.py:96): the tensor is
+        written by simulate itself, nothing to do."""
+
     @property
     def contact_link_indices(self) -> list:
         return contact_link_indices(self.model)

@@ -243,6 +243,15 @@ class VecTask(Env):
         """gym.refresh_net_contact_force_tensor (tasks/anymal.py:117)."""
         self.sim.refresh_net_contact_force_tensor()
 
+    def acquire_dof_force_tensor(self) -> torch.Tensor:
+        """gym.acquire_dof_force_tensor (tasks/MA_OP3.py:91): the sim's live
+        [N, D] tensor of per-DOF actuator forces (Sim)."""
+        return self.sim.acquire_dof_force_tensor()
+
+    def refresh_dof_force_tensor(self):
+        """gym.refresh_dof_force_tensor (tasks/MA_OP3.py:96)."""
+        self.sim.refresh_dof_force_tensor()
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)

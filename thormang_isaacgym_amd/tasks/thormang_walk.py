@@ -21,6 +21,13 @@ contact force tensor: ``contact_forces`` [N,L,3], ``feet_indices`` and
 ``extras["feet_contact_force"]`` [N,2,3] after every step, for foot-contact
 terms a user adds; observation, reward and reset do not read them.  The step
 then runs its post-physics as a separate launch.
+
+``env.enableDofForceSensors: true`` (optional, default false; IsaacGym's
+name) acquires the DOF force tensor: ``dof_forces`` [N,D] and
+``extras["dof_force"]`` after every step -- the actuators' torques of the last
+simulate, for torque, power or saturation terms a user adds.  The reward keeps
+its own ``stiffness * (target - q)`` torque term; observation and reset do not
+read the tensor either.  The step runs unfused as above.
 """
 from __future__ import annotations
 
@@ -83,10 +90,15 @@ class ThormangWalk(VecTask):
         # env.enableContactForces: the per-link ground forces of the last
         # simulate (legged tasks' foot-contact terms, tasks/anymal.py:113-117);
         # observation, reward and reset do not use them
-        self.contact_forces = None
+        self.contact_forces = self.dof_forces = None
         if bool(env.get("enableContactForces", False)):
             self.contact_forces = self.acquire_net_contact_force_tensor()
             self.feet_indices = torch.as_tensor(walk_feet_indices(self.model), dtype=torch.long, device=dev)
+            self._contact_extras()
+        # env.enableDofForceSensors: the actuators' forces of the last simulate
+        # (tasks/MA_OP3.py:91,96,275); observation, reward and reset do not use them
+        if bool(env.get("enableDofForceSensors", False)):
+            self.dof_forces = self.acquire_dof_force_tensor()
             self._contact_extras()
         self.reset_idx(torch.arange(N, device=dev))
 
@@ -166,6 +178,9 @@ class ThormangWalk(VecTask):
         contact force tensor after this step (env.enableContactForces)."""
         if self.contact_forces is not None:
             self.extras["feet_contact_force"] = self.contact_forces[:, self.feet_indices].to(self.rl_device)
+        # extras["dof_force"] [N, D]: the DOF force tensor (env.enableDofForceSensors)
+        if self.dof_forces is not None:
+            self.extras["dof_force"] = self.dof_forces.to(self.rl_device)
 
     def step(self, actions):
         if self.dr_randomizations.get("actions", None) or self.dr_randomizations.get("observations", None):
