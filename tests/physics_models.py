@@ -115,6 +115,119 @@ def landing_checks(zs, vs, rest_offset=0.0, half=0.05):
     return out
 
 
+# ---------------------------------------------------------------- drive / limit / friction known answers
+# One env each; ``step_fn(desc, sp, root, dof, props, pt, vt)`` steps it in place
+# (default: the CPU oracle), ``make_step()`` returns a fresh one per run.  The
+# helpers return what was measured; the tests assert (CPU: test_physics_oracle,
+# GPU: test_gpu_drive_limits, the same bounds).
+def run_steps(state, steps, record, step_fn=None):
+    from tests.oracle_lib import physics_step
+    desc, sp, root, dof, props, pt, vt = state
+    step = step_fn or physics_step
+    out = []
+    for _ in range(steps):
+        step(desc, sp, root, dof, props, pt, vt)
+        out.append(record(root, dof))
+    return np.array(out)
+
+
+def velocity_drive_runs(make_step=None):
+    """A velocity drive (kd 1000) on the pendulum about z, dt 0.01 x 2
+    substeps: the joint velocity over 20 steps towards 7 rad/s with effort 1e6,
+    and over 10 steps (0.1 s) towards 100 rad/s with effort 0.5 -- constant
+    acceleration effort / I, I = 0.01 (the COM lies on the axis).  Returns the
+    two velocity traces."""
+    from thormang_isaacgym_amd.abi import TG_PROP_DAMPING, TG_PROP_DRIVE_MODE, TG_PROP_EFFORT
+    mk = make_step or (lambda: None)
+    out = []
+    for effort, target, steps in ((1e6, 7.0, 20), (0.5, 100.0, 10)):
+        st = sim(pendulum(axis="0 0 1"), dt=0.01, substeps=2, fix_base_link=True)
+        desc, sp, root, dof, props, pt, vt = st
+        props[TG_PROP_DRIVE_MODE, 0, 0] = 2
+        props[TG_PROP_DAMPING, 0, 0] = 1000.0
+        props[TG_PROP_EFFORT, 0, 0] = effort
+        vt[0, 0] = target
+        out.append(run_steps(st, steps, lambda r, d: d[0, 1], mk()))
+    return out
+
+
+def position_drive_run(step_fn=None):
+    """A position drive (kp 3000, kd 300) on the pendulum about z towards
+    0.4 rad: the joint angle over 100 steps."""
+    from thormang_isaacgym_amd.abi import TG_PROP_DAMPING, TG_PROP_DRIVE_MODE, TG_PROP_EFFORT, TG_PROP_STIFFNESS
+    st = sim(pendulum(axis="0 0 1"), dt=0.01, substeps=2, fix_base_link=True)
+    desc, sp, root, dof, props, pt, vt = st
+    props[TG_PROP_DRIVE_MODE, 0, 0] = 1
+    props[TG_PROP_STIFFNESS, 0, 0] = 3000.0
+    props[TG_PROP_DAMPING, 0, 0] = 300.0
+    props[TG_PROP_EFFORT, 0, 0] = 1e6
+    pt[0, 0] = 0.4
+    return run_steps(st, 100, lambda r, d: d[0, 0], step_fn)
+
+
+def joint_limit_run(step_fn=None, through_props=False):
+    """The pendulum about y with a +-0.3 rad window, its fixed base tilted so
+    that gravity swings the arm towards +-pi/2: the joint angle over 300 steps.
+    The window comes from the URDF, or (``through_props``) is set in dof_props
+    on the compiled-in continuous-joint model."""
+    from thormang_isaacgym_amd.abi import TG_PROP_LOWER, TG_PROP_UPPER
+    st = sim(pendulum() if through_props else pendulum(limits=(-0.3, 0.3)), dt=0.01, substeps=2, fix_base_link=True)
+    if through_props:
+        st[4][TG_PROP_LOWER, 0, 0], st[4][TG_PROP_UPPER, 0, 0] = -0.3, 0.3
+    st[3][0, 0] = 0.0
+    st[2][0, 3:7] = [0, np.sin(0.7), 0, np.cos(0.7)]   # tilt the fixed base so gravity has a lever arm
+    return run_steps(st, 300, lambda r, d: d[0, 0], step_fn)
+
+
+def coulomb_slide_run(step_fn=None, mu=0.5, model=None):
+    """A box sliding at 2 m/s on friction ``mu``: (x, vx) over 200 steps and
+    the expected stopping distance v^2 / (2 mu g).  ``model``: the box to use
+    (default: one built with shape friction ``mu``; the caller of another sets
+    the shape friction at run time)."""
+    st = sim(model or box_body(mu=mu), dt=0.005, substeps=1, ground_friction=mu)
+    st[2][0, 2] = 0.05
+    st[2][0, 7] = 2.0
+    return run_steps(st, 200, lambda r, d: r[0, [0, 7]].copy(), step_fn), 2.0 ** 2 / (2 * mu * 9.81)
+
+
+def chain_internal_drive_run(step_fn=None):
+    """Zero gravity, no contact, a velocity drive (kd 5, target 4 rad/s) on the
+    chain's revolute joint: per step the system COM (3) and the joint
+    velocities (2), 500 steps."""
+    from thormang_isaacgym_amd.abi import TG_PROP_DAMPING, TG_PROP_DRIVE_MODE, TG_PROP_EFFORT
+    m = chain()
+    st = sim(m, dt=0.002, substeps=1, gravity=(0, 0, 0))
+    desc, sp, root, dof, props, pt, vt = st
+    props[TG_PROP_DRIVE_MODE, 0, 0] = 2
+    props[TG_PROP_DAMPING, 0, 0] = 5.0
+    props[TG_PROP_EFFORT, 0, 0] = 1e9
+    vt[0, 0] = 4.0
+    return run_steps(st, 500, lambda r, d: np.concatenate([system_com(m, r[0], d[:, 0]), d[:, 1]]), step_fn)
+
+
+def limit_ramp():
+    """TG_LIMIT_RAMP as include/tgsim.h defines it."""
+    import os
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "..", "include", "tgsim.h")) as f:
+        return float(re.search(r"#define\s+TG_LIMIT_RAMP\s+([0-9.eE+-]+)f?", f.read()).group(1))
+
+
+def dof_tree(desc):
+    """Per DOF of a model descriptor: its group and whether that group is a
+    leaf of the group tree (no other group has it as parent)."""
+    a = desc.arrays
+    parent = np.asarray(a["group_parent"])
+    dof_of_group = np.asarray(a["link_dof"])[np.asarray(a["group_root"])]
+    D = len(a["dof_locked"])
+    group, leaf = np.full(D, -1), np.zeros(D, bool)
+    for g in range(1, len(parent)):
+        group[dof_of_group[g]] = g
+        leaf[dof_of_group[g]] = g not in set(parent.tolist())
+    return group, leaf
+
+
 def jit_walker():
     """A URDF that is not compiled into libtgsim.so (run-time load_asset /
     tg_model_jit test): a box torso with two legs, hips driven, one knee

@@ -1,6 +1,11 @@
-"""HIP articulation kernel vs the fp64 oracle on the known-answer models, plus
-the analytic checks themselves on the GPU (free fall, drive steady state,
-resting contact, Coulomb sliding)."""
+"""HIP articulation kernel vs the fp64 oracle on the known-answer models (free
+body, chain, driven pendulum, dropped bodies, the run-time loaded models), the
+link-state and force-tensor reductions, and the analytic checks themselves on
+the GPU: free fall, resting contact, the landing and the contact-offset gate.
+The drive, joint-limit and friction known answers (drive steady state and
+effort limit, position drive, limit against gravity, Coulomb sliding, the
+chain's COM) and the effort / limit / velocity-limit parity are in
+tests/test_gpu_drive_limits.py."""
 import numpy as np
 import pytest
 import torch

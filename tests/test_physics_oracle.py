@@ -74,58 +74,28 @@ def test_torque_free_body_conserves_momentum_and_energy():
 
 def test_chain_internal_drive_keeps_system_com_fixed():
     """Zero gravity, no contact: an internal joint drive must not move the system COM."""
-    m = pm.chain()
-    st = pm.sim(m, dt=0.002, substeps=1, gravity=(0, 0, 0))
-    desc, sp, root, dof, props, pt, vt = st
-    props[TG_PROP_DRIVE_MODE, 0, 0] = 2
-    props[TG_PROP_DAMPING, 0, 0] = 5.0
-    props[TG_PROP_EFFORT, 0, 0] = 1e9
-    vt[0, 0] = 4.0
-    tr = run(st, 500, lambda r, d: np.concatenate([pm.system_com(m, r[0], d[:, 0]), d[:, 1]]))
+    tr = pm.chain_internal_drive_run()
     assert np.all(np.isfinite(tr))
     assert abs(tr[-1, 3] - 4.0) < 0.05          # drive reached its target rate
     assert np.abs(tr[:, :3] - tr[0, :3]).max() < 2e-3
 
 
 def test_velocity_drive_steady_state_and_effort_limit():
-    st = pm.sim(pm.pendulum(axis="0 0 1"), dt=0.01, substeps=2, fix_base_link=True)
-    desc, sp, root, dof, props, pt, vt = st
-    props[TG_PROP_DRIVE_MODE, 0, 0] = 2
-    props[TG_PROP_DAMPING, 0, 0] = 1000.0
-    props[TG_PROP_EFFORT, 0, 0] = 1e6
-    vt[0, 0] = 7.0
-    tr = run(st, 20, lambda r, d: d[0, 1])
-    assert abs(tr[-1] - 7.0) < 1e-3
+    steady, limited = pm.velocity_drive_runs()
+    assert abs(steady[-1] - 7.0) < 1e-3
     # effort-limited: constant acceleration effort / I_pivot
-    st = pm.sim(pm.pendulum(axis="0 0 1"), dt=0.01, substeps=2, fix_base_link=True)
-    desc, sp, root, dof, props, pt, vt = st
-    props[TG_PROP_DRIVE_MODE, 0, 0] = 2
-    props[TG_PROP_DAMPING, 0, 0] = 1000.0
-    props[TG_PROP_EFFORT, 0, 0] = 0.5
-    vt[0, 0] = 100.0
-    tr = run(st, 10, lambda r, d: d[0, 1])
     Ip = 0.01   # COM lies on the vertical axis: only the rotational inertia about z
-    np.testing.assert_allclose(tr[-1], 0.5 / Ip * 0.1, rtol=2e-3)
+    np.testing.assert_allclose(limited[-1], 0.5 / Ip * 0.1, rtol=2e-3)
 
 
 def test_position_drive_converges():
-    st = pm.sim(pm.pendulum(axis="0 0 1"), dt=0.01, substeps=2, fix_base_link=True)
-    desc, sp, root, dof, props, pt, vt = st
-    props[TG_PROP_DRIVE_MODE, 0, 0] = 1
-    props[TG_PROP_STIFFNESS, 0, 0] = 3000.0
-    props[TG_PROP_DAMPING, 0, 0] = 300.0
-    props[TG_PROP_EFFORT, 0, 0] = 1e6
-    pt[0, 0] = 0.4
-    tr = run(st, 100, lambda r, d: d[0, 0])
+    tr = pm.position_drive_run()
     assert abs(tr[-1] - 0.4) < 1e-4
 
 
 def test_joint_limit_holds_against_gravity():
-    st = pm.sim(pm.pendulum(limits=(-0.3, 0.3)), dt=0.01, substeps=2, fix_base_link=True)
-    st[3][0, 0] = 0.0
     # gravity swings the arm towards +-pi/2 around y; the limit must stop it
-    st[2][0, 3:7] = [0, np.sin(0.7), 0, np.cos(0.7)]   # tilt the fixed base so gravity has a lever arm
-    tr = run(st, 300, lambda r, d: d[0, 0])
+    tr = pm.joint_limit_run()
     assert np.abs(tr).max() < 0.36
     assert abs(abs(tr[-1]) - 0.3) < 0.01
 
@@ -143,11 +113,6 @@ def test_resting_contact(shape):
 
 
 def test_coulomb_sliding_distance():
-    mu = 0.5
-    st = pm.sim(pm.box_body(mu=mu), dt=0.005, substeps=1, ground_friction=mu)
-    st[2][0, 2] = 0.05
-    st[2][0, 7] = 2.0
-    tr = run(st, 200, lambda r, d: r[0, [0, 7]].copy())
-    d_exp = 2.0 ** 2 / (2 * mu * 9.81)
+    tr, d_exp = pm.coulomb_slide_run(mu=0.5)
     assert abs(tr[-1, 0] - d_exp) / d_exp < 0.05
     assert abs(tr[-1, 1]) < 1e-3

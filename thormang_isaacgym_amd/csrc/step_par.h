@@ -200,6 +200,7 @@ template <class M> struct ParLayout {
     static constexpr bool SUPER = K > 0 && K * (M::MAXD + 6) <= M::NG * 21;
     static constexpr bool WOOD = M::NG <= 8 && M::NG - 1 <= M::LPE && (SUPER || K == 0);
     static constexpr int WCM = 2;
+    static constexpr float WTE = 1024.f;   // |te| / effort beyond which the rerun is taken (2^-22 x 1024 = 2.4e-4 of the effort)
     static constexpr int WB_G = (TOTAL0 + 3) & ~3;          // [WCM][8]
     static constexpr int WB_R = WB_G + WCM * 8;             // [WCM][6]
     static constexpr int WB_A = WB_R + WCM * 6;             // [WCM][NCG][6]
@@ -1191,6 +1192,13 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
             wmask = (unsigned)(bal >> (lw - sub)) & ((1u << LPE) - 1u);
             wn = __builtin_popcount(wmask);
             if (wn > WCM) { wn = 0; wmask = 0u; return false; }   // more than WCM saturate: the rerun
+            // a clamped drive whose implicit torque te dwarfs its effort: the
+            // update recovers +-effort + (the rest of the joint's bias) from the
+            // first solve's qdd = (te + ...) / D, i.e. only to about 2^-22 |te|
+            // (a kd 1000 velocity drive far from its target on a 0.5 N m effort
+            // accelerated 0.35 % slow); the rerun never forms te
+            const bool big = clm && fabsf(s(gl * GF + F_CL)) > PL::WTE * s(gl * GF + F_CL + 2);
+            if (((unsigned)(__ballot(big) >> (lw - sub)) & ((1u << LPE) - 1u)) != 0u) { wn = 0; wmask = 0u; return false; }
             // (1) lane aidx < wn: the response of the whole tree to a unit torque
             // at clamped group ga (the articulated inertias of the first solve):
             // up-walk along ga's ancestors, root solve, top-down over every group
@@ -1286,19 +1294,20 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
                 Mi[0][0] = Mm[1][1] * id; Mi[1][1] = Mm[0][0] * id;
                 Mi[0][1] = -Mm[0][1] * id; Mi[1][0] = -Mm[1][0] * id;
             }
-            float wv[WCM];
+            // (rhs apart from w: every row of M^-1 takes the whole right-hand side)
+            float rhs[WCM], wv[WCM];
 #pragma unroll
             for (int i = 0; i < WCM; ++i) {
                 float r = qc[i];
 #pragma unroll
                 for (int j = 0; j < WCM; ++j) r += Nm[i][j] * dl[j];
-                wv[i] = r;
+                rhs[i] = r;
             }
 #pragma unroll
             for (int i = 0; i < WCM; ++i) {
                 float z = 0.f;
 #pragma unroll
-                for (int j = 0; j < WCM; ++j) z += Mi[i][j] * wv[j];
+                for (int j = 0; j < WCM; ++j) z += Mi[i][j] * rhs[j];
                 wv[i] = i < wn ? dl[i] + z : 0.f;
             }
             // (3) the corrected accelerations: qdd += G w (the lane's group), a0 += R w
