@@ -46,6 +46,14 @@
  *   tg_set_dof_force_tensor  acquire_dof_force_tensor / refresh_dof_force_tensor
  *                            (tasks/MA_OP3.py:91,96), with
  *                            enable_actor_dof_force_sensors (:275) implied
+ *   tg_jacobians             acquire_jacobian_tensor / refresh_jacobian_tensors
+ *                            (tasks/gogoro/gogoro.py:108-114,396-397,507, the
+ *                            rider's hand IK; tasks/franka_cube_stack.py:389-393,
+ *                            440-441)
+ *   tg_mass_matrices         acquire_mass_matrix_tensor /
+ *                            refresh_mass_matrix_tensors
+ *                            (tasks/franka_cube_stack.py:393,441,
+ *                            operational-space control)
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -295,6 +303,48 @@ int tg_set_net_contact_force_tensor(tg_sim *sim, float *out);
  * after the last simulate; the results are those of that path.  Compiled-in
  * models only: TG_ERR_MODEL for a model from tg_model_jit. */
 int tg_set_dof_force_tensor(tg_sim *sim, float *out);
+/* refresh_jacobian_tensors on the tensor from acquire_jacobian_tensor
+ * (tasks/gogoro/gogoro.py:108-114 "num_envs, num_links, 6, num_dofs + 6"):
+ * out [N, L, 6, 6+D] device, caller-owned, computed on demand from the current
+ * root and dof state, stream-ordered; every element is written, zeros
+ * included.  The generalised velocity is
+ *   u = (root linear velocity, root angular velocity, qd[0..D-1]),
+ * u(0:6) exactly root_state[7:13]: the world-frame velocity of the root
+ * link's centre of mass, then the world-frame angular velocity.  Columns 0..5
+ * are the base, column 6+d is DOF d.  J[e, l] (6 x (6+D)) maps u to the rows
+ * tg_rigid_body_states reports for link l -- the linear velocity of the
+ * link's centre of mass (rows 0..2) and the angular velocity (rows 3..5),
+ * world frame: J[e, l] u == rigid_body_state[e, l, 7:13].  Links in model
+ * order, link 0 is the root.  With c_l the link's centre of mass, a_j the
+ * world axis and p_j the anchor of DOF j's joint: a revolute column is
+ * (a_j x (c_l - p_j), a_j), a prismatic one (a_j, 0); the base columns are the
+ * identity and, for the angular ones, (e_k x (c_l - c_root), e_k).  A column
+ * of a joint that is not on the path from the root to link l is exactly 0.0,
+ * and the linear rows of the three base linear columns are exactly the
+ * identity.  A locked DOF's column is its geometric column at the DOF's
+ * current dof_state position, as tg_rigid_body_states takes it.  All lever
+ * arms are formed relative to the root link's origin, so the result does not
+ * depend on where the env sits on the grid.  With fix_base the call still
+ * writes the full layout; IsaacGym's fixed-base tensor is the view
+ * J[:, 1:, :, 6:]. */
+int tg_jacobians(tg_sim *sim, float *out);
+/* refresh_mass_matrix_tensors on the tensor from acquire_mass_matrix_tensor
+ * (tasks/franka_cube_stack.py:393,441): out [N, 6+D, 6+D] device,
+ * caller-owned, on demand from the current root and dof state,
+ * stream-ordered; every element is written, zeros included.  In the
+ * generalised velocity u of tg_jacobians, with Jv_l / Jw_l the linear and
+ * angular rows of J[e, l]:
+ *   H = sum_l s_l (m_l Jv_l^T Jv_l + Jw_l^T R_l I_l R_l^T Jw_l)
+ *       + diag(0_6, armature),
+ * s_l the env's body mass scale (tg_set_body_mass_scale_indexed: it scales
+ * mass and inertia together, as the step's composites do), I_l the link
+ * inertia about its centre of mass, armature the env's TG_PROP_ARMATURE row.
+ * H[0:6, 0:6] is the whole body's inertia at the root link's centre of mass.
+ * Locked DOFs are ordinary rows and columns, at their dof_state position; the
+ * step's dynamics are those of H with the locked rows and columns removed
+ * (the locked DOFs at the centre of their windows).  H is symmetric bit for
+ * bit.  With fix_base IsaacGym's tensor is the view H[:, 6:, 6:]. */
+int tg_mass_matrices(tg_sim *sim, float *out);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

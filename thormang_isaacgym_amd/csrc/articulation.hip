@@ -133,7 +133,31 @@ int launch_body_states(uint64_t hash, const float *root, const float *dof, int n
     return jit_launch_body_states(hash, root, dof, n, out, stream);
 }
 
-#define TG_RB_FORCES(MODEL)                                                                               \
+#define TG_JACOBIANS(MODEL)                                                                                   \
+    if (hash == MODEL::hash) {                                                                                \
+        hipLaunchKernelGGL(jacobian_kernel<MODEL>, dim3(n), dim3(JAC_THREADS), 0, stream, root, dof, n, out); \
+        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                              \
+    }
+
+int launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
+    TG_FOR_EACH_MODEL(TG_JACOBIANS)
+    return jit_launch_jacobians(hash, root, dof, n, out, stream);
+}
+
+#define TG_MASS_MATRICES(MODEL)                                                                            \
+    if (hash == MODEL::hash) {                                                                             \
+        hipLaunchKernelGGL(mass_matrix_kernel<MODEL>, dim3(n), dim3(64), 0, stream, root, dof, mass_scale, \
+                           props, n, out);                                                                 \
+        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                           \
+    }
+
+int launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                         const float *props, int n, float *out, hipStream_t stream) {
+    TG_FOR_EACH_MODEL(TG_MASS_MATRICES)
+    return jit_launch_mass_matrices(hash, root, dof, mass_scale, props, n, out, stream);
+}
+
+#define TG_RB_FORCES(MODEL)                                                                              \
     if (hash == MODEL::hash) {                                                                            \
         hipLaunchKernelGGL(rb_force_kernel<MODEL>, dim3((n + COMPOSE_WPB - 1) / COMPOSE_WPB), dim3(64 * COMPOSE_WPB), \
                            0, stream, root, dof, comp, n,                                                 \

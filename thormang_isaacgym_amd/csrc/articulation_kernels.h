@@ -708,6 +708,348 @@ template <class M> __global__ __launch_bounds__(64) void body_state_kernel(const
     }
 }
 
+// ---------------------------------------------------------------- Jacobian and mass matrix
+// acquire/refresh_jacobian_tensors and acquire/refresh_mass_matrix_tensors
+// (tgsim.h tg_jacobians / tg_mass_matrices).  Generalised velocity u = (root
+// com velocity, root angular velocity, qd): columns 0..5 the base, 6 + d DOF d.
+// Both kernels take the forward kinematics RELATIVE TO THE ROOT LINK'S ORIGIN
+// (world axes): no absolute position enters, so an env far out on the grid
+// keeps its lever arms and the result is exactly translation invariant.
+
+// per-model tables derived from link_parent / link_dof at compile time
+template <class M> struct JacTables {
+    static constexpr int ND1 = M::ND > 0 ? M::ND : 1;
+    struct DofLink {
+        int v[ND1];
+    };
+    struct Anc {
+        unsigned char v[M::NL * ND1];   // [l][d]: DOF d's joint lies on the path root -> link l
+    };
+    static constexpr DofLink make_dof_link() {
+        DofLink t{};
+        for (int l = 0; l < M::NL; ++l)
+            if (M::link_dof[l] >= 0) t.v[M::link_dof[l]] = l;
+        return t;
+    }
+    static constexpr Anc make_anc() {
+        Anc t{};
+        for (int l = 0; l < M::NL; ++l)
+            for (int k = l; k >= 0; k = M::link_parent[k])
+                if (M::link_dof[k] >= 0) t.v[l * ND1 + M::link_dof[k]] = 1;
+        return t;
+    }
+    static constexpr DofLink dof_link = make_dof_link();   // the link a DOF's joint leads to
+    static constexpr Anc anc = make_anc();
+};
+
+// Link poses relative to the root link's origin, level by level with one
+// wavefront (lane = link): T[l] = R_l (9), p_l - p_root (3); A[l] = the world
+// axis of link l's incoming joint.  Locked DOFs at their dof_state position,
+// as body_state_kernel takes them.  Ends with a wave-level sync.
+template <class M>
+__device__ __forceinline__ void fk_root_relative(const float *r, const float *q, int lane, float (*T)[12],
+                                                 float (*A)[3]) {
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    // each lane's links first, everything that does not depend on the parent:
+    // the joint's placement in the parent frame at q and its axis there -- the
+    // table reads and the sines stay out of the level-by-level chain below
+    constexpr int NP = (M::NL + 63) / 64;   // links per lane
+    M3 Rl[NP];
+    V3 tl[NP], al[NP];
+    int par[NP], dep[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int l = lane + 64 * p;
+        dep[p] = -1;
+        par[p] = -1;
+        if (l >= M::NL) continue;
+        dep[p] = M::link_depth[l];
+        par[p] = M::link_parent[l];
+        if (par[p] < 0) {
+            float qx = r[3], qy = r[4], qz = r[5], qw = r[6];
+            const float in = rsqrtf(qx * qx + qy * qy + qz * qz + qw * qw);
+            Rl[p] = quat_to_m3(qx * in, qy * in, qz * in, qw * in);
+            tl[p] = v3(0.f, 0.f, 0.f);
+            al[p] = v3(0.f, 0.f, 0.f);
+        } else {
+            const float *o = M::link_origin[l];
+            M3 Ro{{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8]}};
+            V3 to = v3(o[9], o[10], o[11]);
+            const int d = M::link_dof[l];
+            const float qq = d >= 0 ? q[2 * d] : 0.f;
+            const float *a = M::link_axis[l];
+            al[p] = mul(Ro, v3(a[0], a[1], a[2]));
+            if (M::link_jtype[l] == TG_JOINT_REVOLUTE)
+                Ro = mul(Ro, rot_axis(a[0], a[1], a[2], qq));
+            else if (M::link_jtype[l] == TG_JOINT_PRISMATIC)
+                to = to + qq * al[p];
+            Rl[p] = Ro;
+            tl[p] = to;
+        }
+    }
+    for (int lev = 0; lev <= M::NDEPTH; ++lev) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            if (dep[p] != lev) continue;
+            const int l = lane + 64 * p;
+            M3 R = Rl[p];
+            V3 P = tl[p], ax = al[p];
+            if (par[p] >= 0) {
+                const int pl = par[p];
+                M3 Rp;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) Rp.a[k] = T[pl][k];
+                R = mul(Rp, Rl[p]);
+                P = v3(T[pl][9], T[pl][10], T[pl][11]) + mul(Rp, tl[p]);
+                ax = mul(Rp, al[p]);
+            }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) T[l][k] = R.a[k];
+            T[l][9] = P.x; T[l][10] = P.y; T[l][11] = P.z;
+            A[l][0] = ax.x; A[l][1] = ax.y; A[l][2] = ax.z;
+        }
+        wsync();
+    }
+}
+
+// Jacobian, out [N, L, 6, 6 + D]: J[e, l] maps u to the rows body_state_kernel
+// reports for link l (com linear velocity, angular velocity).  One workgroup
+// per env: wave 0 runs the forward kinematics and leaves, per link, the joint
+// axis a, the joint anchor p and the link com c in LDS.  Then, a chunk of links
+// at a time (JAC_TILE floats of LDS at most), thread = (link, column) forms the
+// column's 6 rows once -- the base columns are the identity and e_k x (c_l -
+// c_root); DOF d (joint of link j) is 0 unless j is an ancestor-or-self of l,
+// else (a x (c_l - p_j), a) for a revolute joint, (a, 0) for a prismatic one
+// -- into the tile in the tensor's flat order, and all threads stream the tile
+// out, 16 bytes per lane per store (a scalar head and tail where the chunk
+// does not start or end on a 16-byte line; the tile is kept congruent to the
+// global address mod 16 bytes, so the LDS reads are 16 bytes wide too).
+constexpr int JAC_THREADS = 256;
+constexpr int JAC_TILE = 4096;
+
+template <class M>
+__device__ __forceinline__ void jac_column(int l, int col, const float (*A)[3], const float (*T)[12],
+                                           const float (*Cc)[3], V3 &lin, V3 &ang) {
+    using JT = JacTables<M>;
+    const V3 zero = v3(0.f, 0.f, 0.f), c = v3(Cc[l][0], Cc[l][1], Cc[l][2]);
+    lin = zero;
+    ang = zero;
+    if (col < 6) {
+        const int k = col < 3 ? col : col - 3;
+        const V3 ek = v3(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f);
+        if (col < 3) {
+            lin = ek;
+        } else {
+            lin = cross(ek, c - v3(Cc[0][0], Cc[0][1], Cc[0][2]));
+            ang = ek;
+        }
+        return;
+    }
+    const int d = col - 6;
+    if (!JT::anc.v[l * JT::ND1 + d]) return;
+    const int j = JT::dof_link.v[d];
+    const V3 a = v3(A[j][0], A[j][1], A[j][2]);
+    if (M::link_jtype[j] == TG_JOINT_PRISMATIC) {
+        lin = a;
+    } else {
+        lin = cross(a, c - v3(T[j][9], T[j][10], T[j][11]));
+        ang = a;
+    }
+}
+
+template <class M> __global__ __launch_bounds__(JAC_THREADS) void jacobian_kernel(const float *root, const float *dof,
+                                                                                  int n, float *out) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    __shared__ float T[M::NL][12], A[M::NL][3], Cc[M::NL][3];
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        fk_root_relative<M>(root + 13 * (size_t)e, dof + 2 * (size_t)e * M::ND, tid, T, A);
+        for (int l = tid; l < M::NL; l += 64) {
+            M3 R;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+            const V3 c = v3(T[l][9], T[l][10], T[l][11]) +
+                         mul(R, v3(M::link_inertia[l][1], M::link_inertia[l][2], M::link_inertia[l][3]));
+            Cc[l][0] = c.x; Cc[l][1] = c.y; Cc[l][2] = c.z;
+        }
+    }
+    __syncthreads();
+    constexpr int C = 6 + M::ND, LF = 6 * C;   // floats per link
+    constexpr int LC = JAC_TILE / LF < 1 ? 1 : (JAC_TILE / LF < M::NL ? JAC_TILE / LF : M::NL);   // links per chunk
+    __shared__ __align__(16) float tile[LC * LF + 4];
+    float *oe = out + (size_t)e * M::NL * LF;
+    for (int l0 = 0; l0 < M::NL; l0 += LC) {
+        const int nl = M::NL - l0 < LC ? M::NL - l0 : LC, cnt = nl * LF;
+        float *o = oe + (size_t)l0 * LF;
+        const int sh = (int)(((uintptr_t)o >> 2) & 3u);
+        float *t = tile + sh;   // t + k and o + k sit at the same offset within a 16-byte line
+        for (int i = tid; i < nl * C; i += JAC_THREADS) {
+            const int ll = i / C, col = i - ll * C;
+            V3 lin, ang;
+            jac_column<M>(l0 + ll, col, A, T, Cc, lin, ang);
+            float *tc = t + ll * LF + col;
+            tc[0] = lin.x; tc[C] = lin.y; tc[2 * C] = lin.z;
+            tc[3 * C] = ang.x; tc[4 * C] = ang.y; tc[5 * C] = ang.z;
+        }
+        __syncthreads();
+        int head = (4 - sh) & 3;                          // floats up to the next 16-byte line
+        if (((uintptr_t)o & 3u) != 0 || head > cnt) head = cnt;   // (a float tensor is never off by less than 4 bytes)
+        const int nv = (cnt - head) / 4;
+        for (int k = tid; k < head; k += JAC_THREADS) o[k] = t[k];
+        for (int k = tid; k < nv; k += JAC_THREADS)
+            *reinterpret_cast<float4 *>(o + head + 4 * k) = *reinterpret_cast<const float4 *>(t + head + 4 * k);
+        for (int k = head + 4 * nv + tid; k < cnt; k += JAC_THREADS) o[k] = t[k];
+        __syncthreads();
+    }
+}
+
+// Mass matrix, out [N, 6 + D, 6 + D]: H = sum_l s_l (m_l Jv^T Jv + Jw^T R I R^T
+// Jw) + diag(0_6, armature), by the composite-rigid-body algorithm.  One
+// wavefront per env.  Every link's spatial inertia in world axes about the
+// root origin -- mass, first moment, rotational inertia: 10 floats, scaled by
+// the env's mass scale -- is summed into its ancestors' composites (all in one
+// frame, so a composite is a plain sum: links in descending index order, each
+// added to its parent, lane t carrying float t so that program order alone
+// orders the LDS traffic).  Then lane = DOF i: F_i = I^c_i s_i, and the walk
+// up the ancestors j gives H[i][j] = s_j . F_i, written with H[j][i] from the
+// one value; the base rows are F_i's force and its moment about the root com.
+// Lanes 0..5 fill H[0:6, 0:6] from the whole body's composite the same way.
+// H is assembled in an LDS tile (zero-filled first) and streamed out in row
+// bands of MM_TILE floats at most: one band up to 95 DOFs.
+constexpr int MM_TILE = 10240;
+
+struct JointMotion {
+    V3 w, v;   // angular part, linear velocity of the point at the root origin
+};
+// composite (m, h, I about the origin) times a motion: moment about the origin and force
+__device__ __forceinline__ void comp_mul(const float *c, const JointMotion &s, V3 &nn, V3 &ff) {
+    const V3 h = v3(c[1], c[2], c[3]);
+    nn = symmul(c + 4, s.w) + cross(h, s.v);
+    ff = c[0] * s.v + cross(s.w, h);
+}
+
+template <class M>
+__global__ __launch_bounds__(64) void mass_matrix_kernel(const float *root, const float *dof, const float *mass_scale,
+                                                         const float *props, int n, float *out) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    using JT = JacTables<M>;
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    constexpr int C = 6 + M::ND;
+    constexpr int RB = C * C <= MM_TILE ? C : (MM_TILE / C > 0 ? MM_TILE / C : 1);   // rows per band
+    __shared__ float T[M::NL][12], A[M::NL][3], IC[M::NL][10], Ht[RB * C];
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    // the tree tables the ancestor walk chases, in LDS: a dependent chain of
+    // LDS reads instead of one of global reads
+    __shared__ int WP[M::NL], WD[M::NL];   // parent; 4 dof + joint type, -1 without a DOF
+    for (int l = lane; l < M::NL; l += 64) {
+        WP[l] = M::link_parent[l];
+        WD[l] = M::link_dof[l] >= 0 ? 4 * M::link_dof[l] + M::link_jtype[l] : -1;
+    }
+    fk_root_relative<M>(root + 13 * (size_t)e, dof + 2 * (size_t)e * M::ND, lane, T, A);
+    for (int l = lane; l < M::NL; l += 64) {
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const float *li = M::link_inertia[l];
+        const float sc = mass_scale ? mass_scale[(size_t)e * M::NL + l] : 1.f;
+        const float m = sc * li[0];
+        const V3 c = v3(T[l][9], T[l][10], T[l][11]) + mul(R, v3(li[1], li[2], li[3]));
+        float I[6];
+        sym_rot(li + 4, transpose(R), I);   // R I R^T
+        const float c2 = dot(c, c);
+        IC[l][0] = m;
+        IC[l][1] = m * c.x; IC[l][2] = m * c.y; IC[l][3] = m * c.z;
+        IC[l][4] = sc * I[0] + m * (c2 - c.x * c.x);
+        IC[l][5] = sc * I[1] + m * (c2 - c.y * c.y);
+        IC[l][6] = sc * I[2] + m * (c2 - c.z * c.z);
+        IC[l][7] = sc * I[3] - m * c.x * c.y;
+        IC[l][8] = sc * I[4] - m * c.x * c.z;
+        IC[l][9] = sc * I[5] - m * c.y * c.z;
+    }
+    wsync();
+    if (lane < 10) {
+#pragma unroll
+        for (int k = M::NL - 1; k >= 1; --k) IC[M::link_parent[k]][lane] += IC[k][lane];
+    }
+    wsync();
+    // the root link's com relative to its origin, world axes
+    V3 c0;
+    {
+        M3 R0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R0.a[k] = T[0][k];
+        c0 = mul(R0, v3(M::link_inertia[0][1], M::link_inertia[0][2], M::link_inertia[0][3]));
+    }
+    auto joint_motion = [&](int l) {   // of link l's incoming joint
+        const V3 a = v3(A[l][0], A[l][1], A[l][2]);
+        if ((WD[l] & 3) == TG_JOINT_PRISMATIC) return JointMotion{v3(0.f, 0.f, 0.f), a};
+        return JointMotion{a, cross(v3(T[l][9], T[l][10], T[l][11]), a)};
+    };
+    auto base_motion = [&](int k) {   // u[k] = 1: root com velocity e_k, or rotation e_(k-3) about the root com
+        const V3 ek = v3(k % 3 == 0 ? 1.f : 0.f, k % 3 == 1 ? 1.f : 0.f, k % 3 == 2 ? 1.f : 0.f);
+        if (k < 3) return JointMotion{v3(0.f, 0.f, 0.f), ek};
+        return JointMotion{ek, cross(c0, ek)};
+    };
+    float *o = out + (size_t)e * C * C;
+    for (int r0 = 0; r0 < C; r0 += RB) {
+        const int nb = C - r0 < RB ? C - r0 : RB;
+        for (int k = lane; k < nb * C; k += 64) Ht[k] = 0.f;
+        wsync();
+        auto put = [&](int row, int col, float v) {   // H[row][col] and H[col][row], whichever lies in the band
+            if (row >= r0 && row < r0 + nb) Ht[(row - r0) * C + col] = v;
+            if (col >= r0 && col < r0 + nb) Ht[(col - r0) * C + row] = v;
+        };
+        if (lane < 6) {
+            V3 nn, ff;
+            comp_mul(IC[0], base_motion(lane), nn, ff);
+            for (int k = 0; k <= lane; ++k) {
+                const JointMotion s = base_motion(k);
+                put(lane, k, dot(s.w, nn) + dot(s.v, ff));
+            }
+        }
+        for (int i = lane; i < M::ND; i += 64) {
+            const int li = JT::dof_link.v[i];
+            V3 nn, ff;
+            comp_mul(IC[li], joint_motion(li), nn, ff);
+            const float arm = props[((size_t)TG_PROP_ARMATURE * n + e) * M::ND + i];
+            for (int l = li; l > 0; l = WP[l]) {
+                if (WD[l] < 0) continue;
+                const JointMotion s = joint_motion(l);
+                const float v = dot(s.w, nn) + dot(s.v, ff);
+                put(6 + i, 6 + (WD[l] >> 2), l == li ? v + arm : v);
+            }
+            const V3 nc = nn - cross(c0, ff);   // F_i's moment about the root com
+            put(6 + i, 0, ff.x); put(6 + i, 1, ff.y); put(6 + i, 2, ff.z);
+            put(6 + i, 3, nc.x); put(6 + i, 4, nc.y); put(6 + i, 5, nc.z);
+        }
+        wsync();
+        float *ob = o + (size_t)r0 * C;
+        const int cnt = nb * C;
+        int head = (int)(((16u - (unsigned)((uintptr_t)ob & 15u)) & 15u) >> 2);
+        if (((uintptr_t)ob & 3u) != 0 || head > cnt) head = cnt;
+        const int nv = (cnt - head) / 4;
+        for (int k = lane; k < head; k += 64) ob[k] = Ht[k];
+        for (int k = lane; k < nv; k += 64) {
+            const float *h = Ht + head + 4 * k;
+            *reinterpret_cast<float4 *>(ob + head + 4 * k) = make_float4(h[0], h[1], h[2], h[3]);
+        }
+        for (int k = head + 4 * nv + lane; k < cnt; k += 64) ob[k] = Ht[k];
+        wsync();
+    }
+}
+
 // ---------------------------------------------------------------- rigid-body forces
 // apply_rigid_body_force_tensors (reference call site
 // tasks/gogoro_realistic_turning_sim_paper.py:457): per-link forces [N*L,3] at

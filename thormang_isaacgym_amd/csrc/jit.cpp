@@ -35,13 +35,16 @@ namespace tg {
 namespace {
 
 constexpr int JIT_COMPOSE_WPB = 8;   // articulation_kernels.h COMPOSE_WPB
-enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, NK };
+constexpr int JIT_JAC_THREADS = 256;   // articulation_kernels.h JAC_THREADS
+enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, NK };
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, false, tg::NoPost>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, true, tg::NoPost>",
     "tg::body_state_kernel<TgJitModel>",
     "tg::rb_force_kernel<TgJitModel>",
+    "tg::jacobian_kernel<TgJitModel>",
+    "tg::mass_matrix_kernel<TgJitModel>",
 };
 // the per-model launch figures the host needs, read back from the module
 // (tgjit_meta, same order)
@@ -150,7 +153,7 @@ int compile(const std::string &src, const std::string &incdir, JitCode &out, std
     return 0;
 }
 
-// cache file: "TGJIT1\n", one lowered name per line, then the code object
+// cache file: "TGJIT2\n", one lowered name per line, then the code object
 bool cache_load(const std::string &path, JitCode &out) {
     std::string s;
     if (!read_file(path, s)) return false;
@@ -163,7 +166,7 @@ bool cache_load(const std::string &path, JitCode &out) {
         return true;
     };
     std::string magic;
-    if (!line(magic) || magic != "TGJIT1") return false;
+    if (!line(magic) || magic != "TGJIT2") return false;
     for (int k = 0; k < NK; ++k)
         if (!line(out.names[k]) || out.names[k].empty()) return false;
     if (pos >= s.size()) return false;
@@ -176,7 +179,7 @@ void cache_store(const std::string &path, const JitCode &c) {
     {
         std::ofstream f(tmp, std::ios::binary);
         if (!f) return;
-        f << "TGJIT1\n";
+        f << "TGJIT2\n";
         for (int k = 0; k < NK; ++k) f << c.names[k] << "\n";
         f.write(c.code.data(), (std::streamsize)c.code.size());
         if (!f) return;
@@ -305,6 +308,21 @@ int jit_launch_rb_forces(uint64_t hash, const float *root, const float *dof, con
     void *args[] = {&root, &dof, &comp, &n, &mass_scale, &forces, &torques, &space, &out, &props};
     return launch(L->f[K_RBF], (unsigned)((n + JIT_COMPOSE_WPB - 1) / JIT_COMPOSE_WPB), 64 * JIT_COMPOSE_WPB, 0, stream,
                   args);
+}
+
+int jit_launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
+    JitLoaded *L = find(hash);
+    if (!L) return TG_ERR_MODEL;
+    void *args[] = {&root, &dof, &n, &out};
+    return launch(L->f[K_JAC], (unsigned)n, JIT_JAC_THREADS, 0, stream, args);
+}
+
+int jit_launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                             const float *props, int n, float *out, hipStream_t stream) {
+    JitLoaded *L = find(hash);
+    if (!L) return TG_ERR_MODEL;
+    void *args[] = {&root, &dof, &mass_scale, &props, &n, &out};
+    return launch(L->f[K_MASS], (unsigned)n, 64, 0, stream, args);
 }
 
 }  // namespace tg

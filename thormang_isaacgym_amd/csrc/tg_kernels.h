@@ -180,6 +180,11 @@ int launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipSt
                    hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 int compiled_hashes(uint64_t *out, int cap);
 int launch_body_states(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
+// Jacobians [N,L,6,6+D] (jacobian_kernel) and mass matrices [N,6+D,6+D]
+// (mass_matrix_kernel; props = the [TG_NUM_PROPS,N,D] rows, for the armature)
+int launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
+int launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                         const float *props, int n, float *out, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
@@ -201,6 +206,9 @@ int jit_launch_body_states(uint64_t hash, const float *root, const float *dof, i
 int jit_launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                          const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                          const float *props, hipStream_t stream);
+int jit_launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
+int jit_launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                             const float *props, int n, float *out, hipStream_t stream);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

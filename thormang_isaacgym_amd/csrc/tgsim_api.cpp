@@ -709,6 +709,27 @@ int tg_rigid_body_states(tg_sim *s, float *out) {
     return TG_OK;
 }
 
+int tg_jacobians(tg_sim *s, float *out) {
+    if (int rc = check_sim(s)) return rc;
+    if (!out) return fail(TG_ERR_ARG, "tg_jacobians: null output");
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_jacobians(s->hash, s->root, s->dof, (int)s->N, out, s->stream))
+        return fail(rc, "Jacobian launch failed");
+    return TG_OK;
+}
+
+int tg_mass_matrices(tg_sim *s, float *out) {
+    if (int rc = check_sim(s)) return rc;
+    if (!out) return fail(TG_ERR_ARG, "tg_mass_matrices: null output");
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_mass_matrices(s->hash, s->root, s->dof, s->mass_scale, s->props, (int)s->N, out,
+                                          s->stream))
+        return fail(rc, "mass-matrix launch failed");
+    return TG_OK;
+}
+
 int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
     if (int rc = check_sim(s)) return rc;
     if (!out) {

@@ -355,6 +355,43 @@ class Sim:
         """gym.refresh_dof_force_tensor (tasks/MA_OP3.py:96): the tensor is
         written by simulate itself, nothing to do."""
 
+    def acquire_jacobian_tensor(self) -> torch.Tensor:
+        """gym.acquire_jacobian_tensor (tasks/gogoro/gogoro.py:108-114): the link
+        Jacobians, filled by refresh_jacobian_tensors.  Floating base:
+        [N, L, 6, D+6] -- J[e, l] maps u = (root com velocity, root angular
+        velocity, qd) to link l's com linear velocity (rows 0..2) and angular
+        velocity (rows 3..5), world frame, the rows of the rigid-body state
+        tensor (tgsim.h tg_jacobians).  With fix_base, IsaacGym's rule: the
+        view [N, L-1, 6, D] (no root link, no base columns) of the same
+        storage."""
+        if getattr(self, "_jacobian", None) is None:
+            self._jacobian = torch.zeros(self.num_envs, self.L, 6, self.D + 6, dtype=torch.float32,
+                                         device=self.device)
+        return self._jacobian[:, 1:, :, 6:] if self.params.fix_base else self._jacobian
+
+    def refresh_jacobian_tensors(self):
+        """gym.refresh_jacobian_tensors (gogoro.py:396): one kernel launch from
+        the current root and dof state, on the sim's stream."""
+        self.acquire_jacobian_tensor()
+        check(lib().tg_jacobians(self._h, _ptr(self._jacobian)), "refresh_jacobian_tensors")
+
+    def acquire_mass_matrix_tensor(self) -> torch.Tensor:
+        """gym.acquire_mass_matrix_tensor (tasks/franka_cube_stack.py:393): the
+        joint-space inertia in the Jacobian's generalised velocity, filled by
+        refresh_mass_matrix_tensors.  Floating base: [N, D+6, D+6], per-env
+        mass scales and armature included (tgsim.h tg_mass_matrices); with
+        fix_base the view [N, D, D] of the same storage."""
+        if getattr(self, "_mass_matrix", None) is None:
+            self._mass_matrix = torch.zeros(self.num_envs, self.D + 6, self.D + 6, dtype=torch.float32,
+                                            device=self.device)
+        return self._mass_matrix[:, 6:, 6:] if self.params.fix_base else self._mass_matrix
+
+    def refresh_mass_matrix_tensors(self):
+        """gym.refresh_mass_matrix_tensors (franka_cube_stack.py:441): one kernel
+        launch from the current root and dof state, on the sim's stream."""
+        self.acquire_mass_matrix_tensor()
+        check(lib().tg_mass_matrices(self._h, _ptr(self._mass_matrix)), "refresh_mass_matrix_tensors")
+
     @property
     def contact_link_indices(self) -> list:
         return contact_link_indices(self.model)

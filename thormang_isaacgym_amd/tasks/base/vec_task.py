@@ -252,6 +252,24 @@ class VecTask(Env):
         """gym.refresh_dof_force_tensor (tasks/MA_OP3.py:96)."""
         self.sim.refresh_dof_force_tensor()
 
+    def acquire_jacobian_tensor(self) -> torch.Tensor:
+        """gym.acquire_jacobian_tensor (tasks/gogoro/gogoro.py:108-114): the sim's
+        [N, L, 6, D+6] link Jacobians ([N, L-1, 6, D] with a fixed base; Sim)."""
+        return self.sim.acquire_jacobian_tensor()
+
+    def refresh_jacobian_tensors(self):
+        """gym.refresh_jacobian_tensors (tasks/gogoro/gogoro.py:396)."""
+        self.sim.refresh_jacobian_tensors()
+
+    def acquire_mass_matrix_tensor(self) -> torch.Tensor:
+        """gym.acquire_mass_matrix_tensor (tasks/franka_cube_stack.py:393): the
+        sim's [N, D+6, D+6] mass matrices ([N, D, D] with a fixed base; Sim)."""
+        return self.sim.acquire_mass_matrix_tensor()
+
+    def refresh_mass_matrix_tensors(self):
+        """gym.refresh_mass_matrix_tensors (tasks/franka_cube_stack.py:441)."""
+        self.sim.refresh_mass_matrix_tensors()
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)
