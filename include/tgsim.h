@@ -54,6 +54,11 @@
  *                            refresh_mass_matrix_tensors
  *                            (tasks/franka_cube_stack.py:393,441,
  *                            operational-space control)
+ *   tg_ik_dls                the rider's hand IK, damped least squares on one
+ *                            link's Jacobian block added to the position targets
+ *                            (tasks/gogoro/gogoro.py:381-427, with
+ *                            orientation_error :605-608; the one-block control
+ *                            of tasks/franka_cube_stack.py:392,602-628)
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -345,6 +350,67 @@ int tg_jacobians(tg_sim *sim, float *out);
  * (the locked DOFs at the centre of their windows).  H is symmetric bit for
  * bit.  With fix_base IsaacGym's tensor is the view H[:, 6:, 6:]. */
 int tg_mass_matrices(tg_sim *sim, float *out);
+/* Damped-least-squares end-effector IK, the hand IK of
+ * tasks/gogoro/gogoro.py:381-427 in one kernel: for K chains per env, the pose
+ * error of a point on a link to a goal, the step
+ *   u = J^T (J J^T + lambda^2 I)^-1 dpose
+ * on the chain's own Jacobian columns, and optionally the position targets
+ * q + u.  On demand, stream-ordered, computed from the current root and dof
+ * state; nothing else of the sim is read and nothing of it is written.  The
+ * chains array is HOST memory, read during the call and not retained.
+ *
+ * Controlled point and rows, chain k of env e, l = chains[k].link: the
+ * controlled point is x = o_l + R_l offset, o_l the link ORIGIN -- the
+ * position tg_rigid_body_states reports in [0:3] -- and R_l the link's
+ * rotation; not the centre of mass the linear rows of tg_jacobians use.  Jv is
+ * the Jacobian of x: a revolute column is a_j x (x - p_j), a prismatic one a_j
+ * (a_j the world axis, p_j the anchor of the DOF's joint); Jw is the angular
+ * Jacobian, a_j for a revolute column and 0 for a prismatic one.  Only the
+ * chain's DOF columns enter, the base is held fixed.  A chain DOF whose joint
+ * is not on the path from the root to the link has an exactly-0 column, so its
+ * dq is exactly 0.0 (the off-path rule of tg_jacobians).  A locked DOF is an
+ * ordinary column at its dof_state position.
+ *
+ * Pose error (orientation_error, gogoro.py:605-608):
+ *   err[0:3] = (goal_pos - root_pos) - (x - root_pos),
+ * both differences formed relative to the root link's origin before they are
+ * subtracted, so the error does not depend on where the env sits on the grid;
+ *   err[3:6] = vec(q_goal (x) conj(q_l)) s, s = +1 if the product's w >= 0 and
+ * -1 otherwise, quaternions xyzw, q_goal normalised by the kernel.  With
+ * goal_quat NULL the system has the 3 position rows only and err[3:6] is
+ * written as 0.
+ *
+ * Solve: y = (J J^T + lambda^2 I)^-1 err by Cholesky (6 x 6, or 3 x 3 without
+ * goal_quat; SPD since lambda > 0), dq[e, k, c] = (J^T y)_c for c < num_dofs
+ * and exactly 0.0 for the padding c >= num_dofs: every element of dq and err
+ * is written.
+ *
+ * Position targets: with pos_targets, for every DOF d that appears in at least
+ * one chain, pos_targets[e, d] = q[e, d] + sum of dq[e, k, c] over all (k, c)
+ * with dofs[c] == d, in ascending (k, c) order, no atomics; chains may share a
+ * DOF.  No other element of pos_targets is touched, and the targets are not
+ * clamped to the joint limits.
+ *
+ * TG_ERR_ARG (message "tg_ik_dls: ...") for null chains or goal_pos,
+ * num_chains outside 1..TG_IK_MAX_CHAINS, a link outside [0, L), num_dofs
+ * outside 1..TG_IK_MAX_DOFS, a DOF outside [0, D), a DOF twice in one chain,
+ * damping not > 0 or not finite, or dq, err and pos_targets all NULL.  Every
+ * model, run-time (tg_model_jit) ones included. */
+#define TG_IK_MAX_CHAINS 8
+#define TG_IK_MAX_DOFS   8
+typedef struct tg_ik_chain {
+    int32_t link;                   /* end-effector link, model order (tg_rigid_body_states) */
+    int32_t num_dofs;               /* 1..TG_IK_MAX_DOFS */
+    int32_t dofs[TG_IK_MAX_DOFS];   /* DOF indices the solve may move; entries >= num_dofs ignored */
+    float   offset[3];              /* controlled point in the link frame (0 = the link origin) */
+} tg_ik_chain;                      /* 52 bytes */
+int tg_ik_dls(tg_sim *sim, const tg_ik_chain *chains /* HOST */, int32_t num_chains,
+              const float *goal_pos,   /* [N, K, 3] device, world frame as tg_rigid_body_states */
+              const float *goal_quat,  /* [N, K, 4] xyzw device, or NULL: position only (3 rows) */
+              float damping,           /* lambda > 0 */
+              float *dq,               /* [N, K, TG_IK_MAX_DOFS] device or NULL */
+              float *err,              /* [N, K, 6] device or NULL */
+              float *pos_targets);     /* [N, D] device or NULL */
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

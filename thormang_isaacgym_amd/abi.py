@@ -59,6 +59,16 @@ class tg_state_view(C.Structure):
     ]
 
 
+TG_IK_MAX_CHAINS, TG_IK_MAX_DOFS = 8, 8
+
+
+class tg_ik_chain(C.Structure):
+    """One chain of tg_ik_dls (tgsim.h): end-effector link, the DOFs the solve may move, the controlled point."""
+    _fields_ = [
+        ("link", C.c_int32), ("num_dofs", C.c_int32), ("dofs", C.c_int32 * TG_IK_MAX_DOFS), ("offset", C.c_float * 3),
+    ]
+
+
 F2 = C.c_float * 2
 
 

@@ -157,6 +157,20 @@ int launch_mass_matrices(uint64_t hash, const float *root, const float *dof, con
     return jit_launch_mass_matrices(hash, root, dof, mass_scale, props, n, out, stream);
 }
 
+#define TG_IK_DLS(MODEL)                                                                                     \
+    if (hash == MODEL::hash) {                                                                               \
+        hipLaunchKernelGGL(ik_dls_kernel<MODEL>, dim3(n), dim3(64), 0, stream, root, dof, n, ch, K, goal_pos, \
+                           goal_quat, lambda2, dq, err, pos_targets);                                        \
+        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                             \
+    }
+
+int launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
+                  const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
+                  float *pos_targets, hipStream_t stream) {
+    TG_FOR_EACH_MODEL(TG_IK_DLS)
+    return jit_launch_ik_dls(hash, root, dof, n, ch, K, goal_pos, goal_quat, lambda2, dq, err, pos_targets, stream);
+}
+
 #define TG_RB_FORCES(MODEL)                                                                              \
     if (hash == MODEL::hash) {                                                                            \
         hipLaunchKernelGGL(rb_force_kernel<MODEL>, dim3((n + COMPOSE_WPB - 1) / COMPOSE_WPB), dim3(64 * COMPOSE_WPB), \

@@ -1050,6 +1050,185 @@ __global__ __launch_bounds__(64) void mass_matrix_kernel(const float *root, cons
     }
 }
 
+// Damped-least-squares end-effector IK (tgsim.h tg_ik_dls), the hand IK of
+// tasks/gogoro/gogoro.py:381-427 in one launch.  One wavefront per env, K <=
+// TG_IK_MAX_CHAINS chains of at most TG_IK_MAX_DOFS columns each, so one lane
+// holds one (chain, column): lane = 8 k + c.  After the shared forward
+// kinematics (link poses relative to the root origin and joint axes in LDS):
+//   lane k       the controlled point x = o_l + R_l offset (link ORIGIN, not
+//                the com) and the pose error -- position as (goal - root) - (x
+//                - root), orientation vec(q_goal conj(q_l)) with the sign of w
+//   lane (k, c)  the column's rows (a x (x - p_j), a), (a, 0) for a prismatic
+//                joint, exactly 0 off the link's path or past num_dofs
+//   lanes        the 21 (6 without goal_quat) entries of J J^T + lambda^2 I per
+//                chain, each a sum over the 8 columns in column order
+//   lane k       Cholesky and the two triangular solves, in registers
+//   lane (k, c)  dq = column . y
+//   lane d       pos_targets[e, d] = q + the dq of every (k, c) with dofs[c] ==
+//                d, in ascending (k, c) order -- no atomics
+// Wave-level syncs order the LDS traffic, as in fk_root_relative.
+template <int R> __device__ __forceinline__ void ik_chol_solve(const float *g, const float *b, float *y) {
+    // g: lower triangle of an SPD matrix, packed by rows (entry (i, j) at i (i + 1) / 2 + j)
+    float L[R][R], x[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        float d = g[j * (j + 1) / 2 + j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        const float inv = 1.0f / sqrtf(d);
+        L[j][j] = inv;   // the diagonal is kept inverted
+#pragma unroll
+        for (int i = j + 1; i < R; ++i) {
+            float s = g[i * (i + 1) / 2 + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+            L[i][j] = s * inv;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) {   // L z = b
+        float s = b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= L[i][k] * x[k];
+        x[i] = s * L[i][i];
+    }
+#pragma unroll
+    for (int i = R - 1; i >= 0; --i) {   // L^T y = z
+        float s = x[i];
+#pragma unroll
+        for (int k = i + 1; k < R; ++k) s -= L[k][i] * x[k];
+        x[i] = s * L[i][i];
+    }
+#pragma unroll
+    for (int i = 0; i < R; ++i) y[i] = x[i];
+}
+
+template <class M>
+__global__ __launch_bounds__(64) void ik_dls_kernel(const float *root, const float *dof, int n, IkChains ch, int K,
+                                                    const float *goal_pos, const float *goal_quat, float lambda2,
+                                                    float *dq, float *err, float *pos_targets) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    static_assert(TG_IK_MAX_CHAINS * TG_IK_MAX_DOFS <= 64, "one lane per (chain, column)");
+    using JT = JacTables<M>;
+    constexpr int MC = TG_IK_MAX_CHAINS, MD = TG_IK_MAX_DOFS;
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    K = K < 1 ? 1 : (K > MC ? MC : K);
+    __shared__ float T[M::NL][12], A[M::NL][3];
+    __shared__ float X[MC][3], E[MC][6], Jc[MC * MD][6], G[MC][21], Y[MC][6], DQ[MC * MD];
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e, *q = dof + 2 * (size_t)e * M::ND;
+    const bool orient = goal_quat != nullptr;
+    const int NR = orient ? 6 : 3, NT = orient ? 21 : 6;
+    fk_root_relative<M>(r, q, lane, T, A);
+    if (lane < K) {
+        const int k = lane, l = ch.c[k].link;
+        M3 Rl;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Rl.a[i] = T[l][i];
+        const V3 x = v3(T[l][9], T[l][10], T[l][11]) + mul(Rl, v3(ch.c[k].offset[0], ch.c[k].offset[1], ch.c[k].offset[2]));
+        const float *gp = goal_pos + ((size_t)e * K + k) * 3;
+        const V3 el = (v3(gp[0], gp[1], gp[2]) - v3(r[0], r[1], r[2])) - x;
+        V3 eo = v3(0.f, 0.f, 0.f);
+        if (orient) {
+            const float *gq = goal_quat + ((size_t)e * K + k) * 4;
+            float gx = gq[0], gy = gq[1], gz = gq[2], gw = gq[3];
+            const float in = 1.0f / sqrtf(gx * gx + gy * gy + gz * gz + gw * gw);
+            gx *= in; gy *= in; gz *= in; gw *= in;
+            float lx, ly, lz, lw;
+            m3_to_quat(Rl, lx, ly, lz, lw);
+            // q_goal (x) conj(q_l)
+            const V3 gv = v3(gx, gy, gz), lv = v3(lx, ly, lz);
+            const float w = gw * lw + dot(gv, lv);
+            const V3 v = (lw * gv - gw * lv) - cross(gv, lv);
+            eo = w >= 0.f ? v : -v;
+        }
+        X[k][0] = x.x; X[k][1] = x.y; X[k][2] = x.z;
+        E[k][0] = el.x; E[k][1] = el.y; E[k][2] = el.z;
+        E[k][3] = eo.x; E[k][4] = eo.y; E[k][5] = eo.z;
+        if (err) {
+            float *o = err + ((size_t)e * K + k) * 6;
+            o[0] = el.x; o[1] = el.y; o[2] = el.z;
+            o[3] = eo.x; o[4] = eo.y; o[5] = eo.z;
+        }
+    }
+    wsync();
+    const int ck = lane / MD, cc = lane % MD;   // this lane's (chain, column)
+    bool live = false;                          // a column on the link's path
+    {
+        V3 lin = v3(0.f, 0.f, 0.f), ang = v3(0.f, 0.f, 0.f);
+        if (ck < K && cc < ch.c[ck].num_dofs) {
+            const int l = ch.c[ck].link, d = ch.c[ck].dofs[cc];
+            if (JT::anc.v[l * JT::ND1 + d]) {
+                live = true;
+                const int j = JT::dof_link.v[d];
+                const V3 a = v3(A[j][0], A[j][1], A[j][2]);
+                if (M::link_jtype[j] == TG_JOINT_PRISMATIC) {
+                    lin = a;
+                } else {
+                    lin = cross(a, v3(X[ck][0], X[ck][1], X[ck][2]) - v3(T[j][9], T[j][10], T[j][11]));
+                    ang = a;
+                }
+            }
+        }
+        Jc[lane][0] = lin.x; Jc[lane][1] = lin.y; Jc[lane][2] = lin.z;
+        Jc[lane][3] = ang.x; Jc[lane][4] = ang.y; Jc[lane][5] = ang.z;
+    }
+    wsync();
+    for (int i = lane; i < K * NT; i += 64) {
+        const int k = i / NT, t = i - k * NT;
+        const int rr = t >= 15 ? 5 : (t >= 10 ? 4 : (t >= 6 ? 3 : (t >= 3 ? 2 : (t >= 1 ? 1 : 0))));
+        const int ss = t - rr * (rr + 1) / 2;
+        float s = rr == ss ? lambda2 : 0.f;
+#pragma unroll
+        for (int c = 0; c < MD; ++c) s += Jc[k * MD + c][rr] * Jc[k * MD + c][ss];
+        G[k][t] = s;
+    }
+    wsync();
+    if (lane < K) {
+        float g[21], b[6], y[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) b[i] = E[lane][i];
+        if (orient) {
+#pragma unroll
+            for (int i = 0; i < 21; ++i) g[i] = G[lane][i];
+            ik_chol_solve<6>(g, b, y);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) g[i] = G[lane][i];
+            ik_chol_solve<3>(g, b, y);
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) Y[lane][i] = y[i];
+    }
+    wsync();
+    if (ck < K) {
+        float u = 0.f;
+        if (live)
+            for (int i = 0; i < NR; ++i) u += Jc[lane][i] * Y[ck][i];
+        DQ[lane] = u;
+        if (dq) dq[((size_t)e * K + ck) * MD + cc] = u;
+    }
+    if (!pos_targets) return;
+    wsync();
+    for (int d = lane; d < M::ND; d += 64) {
+        float s = 0.f;
+        bool hit = false;
+        for (int k = 0; k < K; ++k)
+            for (int c = 0; c < ch.c[k].num_dofs; ++c)
+                if (ch.c[k].dofs[c] == d) {
+                    s += DQ[k * MD + c];
+                    hit = true;
+                }
+        if (hit) pos_targets[(size_t)e * M::ND + d] = q[2 * d] + s;
+    }
+}
+
 // ---------------------------------------------------------------- rigid-body forces
 // apply_rigid_body_force_tensors (reference call site
 // tasks/gogoro_realistic_turning_sim_paper.py:457): per-link forces [N*L,3] at

@@ -36,7 +36,7 @@ namespace {
 
 constexpr int JIT_COMPOSE_WPB = 8;   // articulation_kernels.h COMPOSE_WPB
 constexpr int JIT_JAC_THREADS = 256;   // articulation_kernels.h JAC_THREADS
-enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, NK };
+enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, NK };
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, false, tg::NoPost>",
@@ -45,6 +45,7 @@ const char *const KERNEL_EXPR[NK] = {
     "tg::rb_force_kernel<TgJitModel>",
     "tg::jacobian_kernel<TgJitModel>",
     "tg::mass_matrix_kernel<TgJitModel>",
+    "tg::ik_dls_kernel<TgJitModel>",
 };
 // the per-model launch figures the host needs, read back from the module
 // (tgjit_meta, same order)
@@ -153,7 +154,7 @@ int compile(const std::string &src, const std::string &incdir, JitCode &out, std
     return 0;
 }
 
-// cache file: "TGJIT2\n", one lowered name per line, then the code object
+// cache file: "TGJIT3\n", one lowered name per line, then the code object
 bool cache_load(const std::string &path, JitCode &out) {
     std::string s;
     if (!read_file(path, s)) return false;
@@ -166,7 +167,7 @@ bool cache_load(const std::string &path, JitCode &out) {
         return true;
     };
     std::string magic;
-    if (!line(magic) || magic != "TGJIT2") return false;
+    if (!line(magic) || magic != "TGJIT3") return false;
     for (int k = 0; k < NK; ++k)
         if (!line(out.names[k]) || out.names[k].empty()) return false;
     if (pos >= s.size()) return false;
@@ -179,7 +180,7 @@ void cache_store(const std::string &path, const JitCode &c) {
     {
         std::ofstream f(tmp, std::ios::binary);
         if (!f) return;
-        f << "TGJIT2\n";
+        f << "TGJIT3\n";
         for (int k = 0; k < NK; ++k) f << c.names[k] << "\n";
         f.write(c.code.data(), (std::streamsize)c.code.size());
         if (!f) return;
@@ -323,6 +324,16 @@ int jit_launch_mass_matrices(uint64_t hash, const float *root, const float *dof,
     if (!L) return TG_ERR_MODEL;
     void *args[] = {&root, &dof, &mass_scale, &props, &n, &out};
     return launch(L->f[K_MASS], (unsigned)n, 64, 0, stream, args);
+}
+
+int jit_launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
+                      const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
+                      float *pos_targets, hipStream_t stream) {
+    JitLoaded *L = find(hash);
+    if (!L) return TG_ERR_MODEL;
+    IkChains cc = ch;
+    void *args[] = {&root, &dof, &n, &cc, &K, &goal_pos, &goal_quat, &lambda2, &dq, &err, &pos_targets};
+    return launch(L->f[K_IK], (unsigned)n, 64, 0, stream, args);
 }
 
 }  // namespace tg

@@ -16,6 +16,11 @@ namespace tg {
 
 constexpr int TG_PM_MAX_DOF = 64;   // prologue lanes: one wavefront per env, lane = dof
 
+// the chains of a tg_ik_dls call, passed to ik_dls_kernel by value (416 bytes)
+struct IkChains {
+    tg_ik_chain c[TG_IK_MAX_CHAINS];
+};
+
 // optional Gogoro pre-physics prologue of the compose launch (tg_gogoro_step)
 struct GogoroPre {
     const float *actions;     // [N] (null: none)
@@ -185,6 +190,10 @@ int launch_body_states(uint64_t hash, const float *root, const float *dof, int n
 int launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
 int launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                          const float *props, int n, float *out, hipStream_t stream);
+// damped-least-squares IK of K chains per env (ik_dls_kernel; tgsim.h tg_ik_dls)
+int launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
+                  const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
+                  float *pos_targets, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
@@ -209,6 +218,9 @@ int jit_launch_rb_forces(uint64_t hash, const float *root, const float *dof, con
 int jit_launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
 int jit_launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                              const float *props, int n, float *out, hipStream_t stream);
+int jit_launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
+                      const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
+                      float *pos_targets, hipStream_t stream);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

@@ -730,6 +730,40 @@ int tg_mass_matrices(tg_sim *s, float *out) {
     return TG_OK;
 }
 
+int tg_ik_dls(tg_sim *s, const tg_ik_chain *chains, int32_t num_chains, const float *goal_pos,
+              const float *goal_quat, float damping, float *dq, float *err, float *pos_targets) {
+    if (int rc = check_sim(s)) return rc;
+    if (!chains || !goal_pos) return fail(TG_ERR_ARG, "tg_ik_dls: null %s", !chains ? "chains" : "goal_pos");
+    if (num_chains < 1 || num_chains > TG_IK_MAX_CHAINS)
+        return fail(TG_ERR_ARG, "tg_ik_dls: num_chains %d outside 1..%d", num_chains, TG_IK_MAX_CHAINS);
+    if (!(damping > 0.f) || !std::isfinite(damping))
+        return fail(TG_ERR_ARG, "tg_ik_dls: damping %g is not a finite number > 0", (double)damping);
+    if (!dq && !err && !pos_targets) return fail(TG_ERR_ARG, "tg_ik_dls: dq, err and pos_targets are all null");
+    tg::IkChains ch{};
+    for (int k = 0; k < num_chains; ++k) {
+        const tg_ik_chain &c = chains[k];
+        if (c.link < 0 || c.link >= s->L)
+            return fail(TG_ERR_ARG, "tg_ik_dls: chain %d: link %d outside [0, %d)", k, c.link, s->L);
+        if (c.num_dofs < 1 || c.num_dofs > TG_IK_MAX_DOFS)
+            return fail(TG_ERR_ARG, "tg_ik_dls: chain %d: num_dofs %d outside 1..%d", k, c.num_dofs, TG_IK_MAX_DOFS);
+        for (int i = 0; i < c.num_dofs; ++i) {
+            if (c.dofs[i] < 0 || c.dofs[i] >= s->D)
+                return fail(TG_ERR_ARG, "tg_ik_dls: chain %d: DOF %d outside [0, %d)", k, c.dofs[i], s->D);
+            for (int j = 0; j < i; ++j)
+                if (c.dofs[j] == c.dofs[i])
+                    return fail(TG_ERR_ARG, "tg_ik_dls: chain %d: DOF %d appears twice", k, c.dofs[i]);
+        }
+        ch.c[k] = c;
+        for (int i = c.num_dofs; i < TG_IK_MAX_DOFS; ++i) ch.c[k].dofs[i] = 0;   // ignored entries: nothing stale reaches the kernel
+    }
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_ik_dls(s->hash, s->root, s->dof, (int)s->N, ch, num_chains, goal_pos, goal_quat,
+                                   damping * damping, dq, err, pos_targets, s->stream))
+        return fail(rc, "tg_ik_dls: launch failed");
+    return TG_OK;
+}
+
 int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
     if (int rc = check_sim(s)) return rc;
     if (!out) {

@@ -392,6 +392,100 @@ class Sim:
         self.acquire_mass_matrix_tensor()
         check(lib().tg_mass_matrices(self._h, _ptr(self._mass_matrix)), "refresh_mass_matrix_tensors")
 
+    def _name_index(self, what: str, x) -> int:
+        """index of a link / DOF given by name or index"""
+        if isinstance(x, str):
+            if what == "link":
+                names = self.model.link_names if isinstance(self.model, NativeModel) else \
+                    [l.name for l in self.model.links]
+            else:
+                names = self.model.dof_names
+            if x not in names:
+                raise KeyError(f"no {what} named {x!r}")
+            return list(names).index(x)
+        return int(x)
+
+    def ik_chain(self, link, dofs=None, num_dofs=None, offset=(0.0, 0.0, 0.0)) -> abi.tg_ik_chain:
+        """One chain of ``solve_ik`` (tgsim.h tg_ik_chain): the end-effector
+        ``link`` and the ``dofs`` the solve may move, names or indices, at most
+        8; ``offset`` is the controlled point in the link frame.  With
+        ``dofs=None`` the chain is the DOFs on the path root -> link in that
+        order, the last ``num_dofs`` of them (default: all, at most 8) -- the
+        rider's arm of tasks/gogoro/gogoro.py:396-397 is
+        ``ik_chain("r_arm_end_link", num_dofs=7)``."""
+        d = self.desc.desc
+        l = self._name_index("link", link)
+        if not 0 <= l < self.L:
+            raise ValueError(f"link {link!r} outside [0, {self.L})")
+        if dofs is None:
+            path, k = [], l
+            while k >= 0:
+                if d.link_dof[k] >= 0:
+                    path.append(int(d.link_dof[k]))
+                k = int(d.link_parent[k])
+            path.reverse()
+            keep = min(len(path), abi.TG_IK_MAX_DOFS) if num_dofs is None else int(num_dofs)
+            if not 1 <= keep <= min(len(path), abi.TG_IK_MAX_DOFS):
+                raise ValueError(f"num_dofs {num_dofs} outside 1..{min(len(path), abi.TG_IK_MAX_DOFS)} for link "
+                                 f"{link!r} ({len(path)} DOFs on its path)")
+            idx = path[len(path) - keep:]
+        else:
+            idx = [self._name_index("dof", x) for x in dofs]
+            if num_dofs is not None and int(num_dofs) != len(idx):
+                raise ValueError(f"num_dofs {num_dofs} does not match the {len(idx)} dofs given")
+            if not 1 <= len(idx) <= abi.TG_IK_MAX_DOFS:
+                raise ValueError(f"a chain takes 1..{abi.TG_IK_MAX_DOFS} DOFs, got {len(idx)}")
+        c = abi.tg_ik_chain()
+        c.link, c.num_dofs = l, len(idx)
+        for i, x in enumerate(idx):
+            c.dofs[i] = x
+        c.offset[:] = [float(v) for v in offset]
+        return c
+
+    def solve_ik(self, chains, goal_pos: torch.Tensor, goal_quat: torch.Tensor | None = None, damping: float = 0.3,
+                 targets: torch.Tensor | None = None, return_error: bool = False):
+        """The hand IK of tasks/gogoro/gogoro.py:381-427 in one kernel launch
+        (tgsim.h tg_ik_dls): for each of the K ``chains`` (``ik_chain``) the
+        damped-least-squares step ``J^T (J J^T + damping^2 I)^-1 dpose``
+        towards ``goal_pos`` [N, K, 3] and ``goal_quat`` [N, K, 4] (xyzw; None:
+        position only), from the current root and dof state, on the sim's
+        stream.  Returns ``dq`` [N, K, 8] (columns past a chain's DOFs are 0),
+        with ``return_error`` also the pose error [N, K, 6]; both are owned by
+        the sim and overwritten by the next call with as many chains.  With
+        ``targets`` [N, D] (e.g. ``dof_pos_target``) the kernel also writes
+        ``q + dq`` (summed over the chains that share a DOF) into the chain
+        DOFs' columns and leaves the others alone."""
+        chains = list(chains)
+        K = len(chains)
+        if not 1 <= K <= abi.TG_IK_MAX_CHAINS:
+            raise ValueError(f"solve_ik takes 1..{abi.TG_IK_MAX_CHAINS} chains, got {K}")
+
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        N = self.num_envs
+        checked(goal_pos, (N, K, 3), "goal_pos")
+        if goal_quat is not None:
+            checked(goal_quat, (N, K, 4), "goal_quat")
+        if targets is not None:
+            checked(targets, (N, self.D), "targets")
+        out = getattr(self, "_ik_out", None)
+        if out is None:
+            out = self._ik_out = {}
+        if K not in out:
+            out[K] = (torch.zeros(N, K, abi.TG_IK_MAX_DOFS, dtype=torch.float32, device=self.device),
+                      torch.zeros(N, K, 6, dtype=torch.float32, device=self.device))
+        dq, err = out[K]
+        arr = (abi.tg_ik_chain * K)(*chains)
+        check(lib().tg_ik_dls(self._h, arr, K, _ptr(goal_pos), _ptr(goal_quat), float(damping), _ptr(dq), _ptr(err),
+                              _ptr(targets)), "solve_ik")
+        return (dq, err) if return_error else dq
+
     @property
     def contact_link_indices(self) -> list:
         return contact_link_indices(self.model)

@@ -270,6 +270,17 @@ class VecTask(Env):
         """gym.refresh_mass_matrix_tensors (tasks/franka_cube_stack.py:441)."""
         self.sim.refresh_mass_matrix_tensors()
 
+    def ik_chain(self, link, dofs=None, num_dofs=None, offset=(0.0, 0.0, 0.0)):
+        """One chain for solve_ik: an end-effector link and the DOFs that may move (Sim.ik_chain)."""
+        return self.sim.ik_chain(link, dofs=dofs, num_dofs=num_dofs, offset=offset)
+
+    def solve_ik(self, chains, goal_pos, goal_quat=None, damping=0.3, targets=None, return_error=False):
+        """The hand IK of tasks/gogoro/gogoro.py:381-427 in one kernel launch:
+        damped-least-squares steps [N, K, 8] towards the goals, optionally
+        written into ``targets`` [N, D] as q + dq (Sim.solve_ik)."""
+        return self.sim.solve_ik(chains, goal_pos, goal_quat=goal_quat, damping=damping, targets=targets,
+                                 return_error=return_error)
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)
