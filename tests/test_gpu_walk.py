@@ -178,6 +178,50 @@ def test_gpu_walk_fused_step_equals_separate_calls():
         assert n_reset > 0, task   # the comparison covered resets
 
 
+def test_gpu_walk_declined_fused_step_equals_separate_calls():
+    """tg_walk_step on a heightfield: the fused walk epilogue has no terrain
+    instantiation, so the launch layer itself declines the fused launch (rc 1,
+    nothing launched) and the call takes its general path -- the heightfield
+    instantiation of the plain step kernel and walk_post_kernel, the very
+    kernels of the separate calls (VecTask.step).  Teacher-forced as above, so
+    everything must be bit-identical.  24 envs: one full and one partial
+    workgroup of 16; the episode is 5 steps long, so timeout resets fall
+    inside the 12 steps."""
+    _cuda()
+    import thormang_isaacgym_amd as tia
+    from thormang_isaacgym_amd.cfg import load_task_cfg
+    from thormang_isaacgym_amd.tasks.base.vec_task import VecTask
+    n, steps = 24, 12
+    envs = []
+    for _ in range(2):
+        cfg = load_task_cfg("ThormangWalk", num_envs=n)
+        cfg["env"]["episodeLength_s"] = 5 * float(cfg["sim"]["dt"]) * cfg["env"].get("controlFrequencyInv", 1)
+        env = tia.make(seed=11, task="ThormangWalk", num_envs=n, sim_device="cuda:0", rl_device="cuda:0", cfg=cfg)
+        # all zeros: the physics of the plane, computed by the heightfield kernel
+        env.sim.set_heightfield(np.zeros((64, 64), np.float32), 1.0, 1.0, -16.0, -16.0, friction=1.0)
+        envs.append(env)
+    f, u = envs
+    assert f.max_episode_length < steps
+    g = torch.Generator(device="cuda:0").manual_seed(5)
+    n_reset = n_timeout = 0
+    for _ in range(steps):
+        for name in ("obs_buf", "rew_buf", "reset_buf", "progress_buf", "actions", "last_actions", "commands"):
+            getattr(u, name).copy_(getattr(f, name))
+        for name in ("root_state", "dof_state"):
+            getattr(u.sim, name).copy_(getattr(f.sim, name))
+        a = torch.rand(n, 33, device="cuda:0", generator=g) * 2.4 - 1.2   # some beyond the clip
+        f.step(a)
+        VecTask.step(u, a)
+        torch.cuda.synchronize()
+        for name in ("obs_buf", "rew_buf", "reset_buf", "progress_buf", "actions"):
+            assert torch.equal(getattr(f, name), getattr(u, name)), name
+        for name in ("dof_pos_target", "root_state", "dof_state"):
+            assert torch.equal(getattr(f.sim, name), getattr(u.sim, name)), name
+        n_reset += int(f.reset_buf.sum())
+        n_timeout += int(f.timeout_buf.sum())
+    assert n_reset > 0 and n_timeout > 0, (n_reset, n_timeout)   # the comparison covered timeout resets
+
+
 def test_gpu_wholebody_kneel_matches_oracle():
     """Whole-body contact (model thormang_wb: feet, shins and hands collide):
     the kneel-and-fall scenario (tests.gpu_harness.walk_kneel_cfg) teacher-

@@ -29,53 +29,30 @@
 
 namespace tg {
 
-// dispatch: this unit's models, then the humanoid unit's
-// (articulation_tree.hip), then the run-time (hipRTC) models
-int launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
-    int rc = unit_launch_step(hash, a, stream, ev_begin, ev_end);
-    if (rc == TG_OTHER_UNIT) rc = tree_launch_step(hash, a, stream, ev_begin, ev_end);
-    return rc == TG_OTHER_UNIT ? jit_launch_step(hash, a, stream, ev_begin, ev_end) : rc;
+// the compiled-in models' dispatch: this unit's, then the humanoid unit's
+// (articulation_tree.hip); TG_OTHER_UNIT: compiled into neither
+template <class P>
+static int compiled_launch(uint64_t hash, const StepArgs &a, const typename P::Args &pa, hipStream_t stream,
+                           hipEvent_t ev_begin, hipEvent_t ev_end) {
+    const int rc = unit_launch<P>(hash, a, pa, stream, ev_begin, ev_end);
+    return rc == TG_OTHER_UNIT ? tree_launch<P>(hash, a, pa, stream, ev_begin, ev_end) : rc;
 }
 
-// the step with the net contact force export: compiled-in models only
-int launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
-                   hipEvent_t ev_end) {
-    int rc = unit_launch_step_cf(hash, a, cf, stream, ev_begin, ev_end);
-    if (rc == TG_OTHER_UNIT) rc = tree_launch_step_cf(hash, a, cf, stream, ev_begin, ev_end);
-    return rc == TG_OTHER_UNIT ? TG_ERR_MODEL : rc;
-}
-
-// the step with the DOF force export (and the contact one when cf is set):
-// compiled-in models only
-int launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream, hipEvent_t ev_begin,
-                   hipEvent_t ev_end) {
-    int rc = unit_launch_step_df(hash, a, cf, df, stream, ev_begin, ev_end);
-    if (rc == TG_OTHER_UNIT) rc = tree_launch_step_df(hash, a, cf, df, stream, ev_begin, ev_end);
-    return rc == TG_OTHER_UNIT ? TG_ERR_MODEL : rc;
-}
-
-int launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
-                       hipEvent_t ev_begin, hipEvent_t ev_end) {
-    int rc = unit_launch_step_gogoro(hash, a, pa, stream, ev_begin, ev_end);
-    if (rc == TG_OTHER_UNIT) rc = tree_launch_step_gogoro(hash, a, pa, stream, ev_begin, ev_end);
+int launch_step(uint64_t hash, const StepArgs &a, const StepPost &post, hipStream_t stream, hipEvent_t ev_begin,
+                hipEvent_t ev_end) {
+    int rc = 0;
+    if (post.walk) rc = compiled_launch<WalkPost>(hash, a, *post.walk, stream, ev_begin, ev_end);
+    else if (post.gogoro) rc = compiled_launch<GogoroPost>(hash, a, *post.gogoro, stream, ev_begin, ev_end);
+    else if (post.paper) rc = compiled_launch<PaperPost>(hash, a, *post.paper, stream, ev_begin, ev_end);
+    else if (post.df) rc = compiled_launch<NoPostDF>(hash, a, {post.cf, post.df}, stream, ev_begin, ev_end);
+    else if (post.cf) rc = compiled_launch<NoPostCF>(hash, a, {post.cf}, stream, ev_begin, ev_end);
+    else rc = compiled_launch<NoPost>(hash, a, {}, stream, ev_begin, ev_end);
     if (rc != TG_OTHER_UNIT) return rc;
-    return jit_has(hash) ? 1 : TG_ERR_MODEL;   // run-time models: no fused epilogue
-}
-
-int launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPostArgs &pa, hipStream_t stream,
-                     hipEvent_t ev_begin, hipEvent_t ev_end) {
-    int rc = unit_launch_step_walk(hash, a, pa, stream, ev_begin, ev_end);
-    if (rc == TG_OTHER_UNIT) rc = tree_launch_step_walk(hash, a, pa, stream, ev_begin, ev_end);
-    if (rc != TG_OTHER_UNIT) return rc;
-    return jit_has(hash) ? 1 : TG_ERR_MODEL;
-}
-
-int launch_step_paper(uint64_t hash, const StepArgs &a, const PaperPostArgs &pa, hipStream_t stream,
-                      hipEvent_t ev_begin, hipEvent_t ev_end) {
-    int rc = unit_launch_step_paper(hash, a, pa, stream, ev_begin, ev_end);
-    if (rc == TG_OTHER_UNIT) rc = tree_launch_step_paper(hash, a, pa, stream, ev_begin, ev_end);
-    if (rc != TG_OTHER_UNIT) return rc;
-    return jit_has(hash) ? 1 : TG_ERR_MODEL;
+    // the run-time (hipRTC) models have the plain step only: no fused epilogue
+    // (the caller falls back), no export
+    if (post.fused()) return jit_has(hash) ? 1 : TG_ERR_MODEL;
+    if (post.cf || post.df) return TG_ERR_MODEL;
+    return jit_launch_step(hash, a, stream, ev_begin, ev_end);
 }
 
 #ifdef TG_DUMP_ENV
@@ -119,106 +96,84 @@ extern "C" int tg_prof_read(unsigned long long *out, int n) {
 }
 #endif
 
+int compiled_hashes(uint64_t *out, int cap) {
+    int n = 0;
 #define TG_HASH(MODEL) if (n < cap) out[n] = MODEL::hash; ++n;
-#define TG_KC(MODEL) if (hash == MODEL::hash) return MODEL::KC;
+    TG_FOR_EACH_MODEL(TG_HASH)
+#undef TG_HASH
+    return n;
+}
 
-#define TG_BODY_STATES(MODEL)                                                                              \
-    if (hash == MODEL::hash) {                                                                             \
-        hipLaunchKernelGGL(body_state_kernel<MODEL>, dim3(n), dim3(64), 0, stream, root, dof, n, out);   \
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                           \
-    }
+// f(M{}) for the compiled-in model M with this hash; false: there is none
+template <class F> static bool with_model(uint64_t hash, F &&f) {
+#define TG_WITH_MODEL(MODEL) if (hash == MODEL::hash) return f(MODEL{}), true;
+    TG_FOR_EACH_MODEL(TG_WITH_MODEL)
+#undef TG_WITH_MODEL
+    return false;
+}
+
+ModelInfo model_info(uint64_t hash) {
+    ModelInfo i;
+    with_model(hash, [&](auto m) { i = {m.KC, m.NTL, m.EPB, m.FUSED}; });
+    return i;
+}
+
+// the on-demand kernels: a compiled-in model's instantiation, else the
+// run-time model's (jit.cpp)
+template <class... P, class... A>
+static int run(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
+    return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
+}
 
 int launch_body_states(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
-    TG_FOR_EACH_MODEL(TG_BODY_STATES)
-    return jit_launch_body_states(hash, root, dof, n, out, stream);
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(body_state_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, n, out);
+    }) ? rc : jit_launch_body_states(hash, root, dof, n, out, stream);
 }
-
-#define TG_JACOBIANS(MODEL)                                                                                   \
-    if (hash == MODEL::hash) {                                                                                \
-        hipLaunchKernelGGL(jacobian_kernel<MODEL>, dim3(n), dim3(JAC_THREADS), 0, stream, root, dof, n, out); \
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                              \
-    }
 
 int launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
-    TG_FOR_EACH_MODEL(TG_JACOBIANS)
-    return jit_launch_jacobians(hash, root, dof, n, out, stream);
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(jacobian_kernel<decltype(m)>, dim3(n), dim3(JAC_THREADS), stream, root, dof, n, out);
+    }) ? rc : jit_launch_jacobians(hash, root, dof, n, out, stream);
 }
-
-#define TG_MASS_MATRICES(MODEL)                                                                            \
-    if (hash == MODEL::hash) {                                                                             \
-        hipLaunchKernelGGL(mass_matrix_kernel<MODEL>, dim3(n), dim3(64), 0, stream, root, dof, mass_scale, \
-                           props, n, out);                                                                 \
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                           \
-    }
 
 int launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                          const float *props, int n, float *out, hipStream_t stream) {
-    TG_FOR_EACH_MODEL(TG_MASS_MATRICES)
-    return jit_launch_mass_matrices(hash, root, dof, mass_scale, props, n, out, stream);
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(mass_matrix_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, props, n, out);
+    }) ? rc : jit_launch_mass_matrices(hash, root, dof, mass_scale, props, n, out, stream);
 }
-
-#define TG_IK_DLS(MODEL)                                                                                     \
-    if (hash == MODEL::hash) {                                                                               \
-        hipLaunchKernelGGL(ik_dls_kernel<MODEL>, dim3(n), dim3(64), 0, stream, root, dof, n, ch, K, goal_pos, \
-                           goal_quat, lambda2, dq, err, pos_targets);                                        \
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                             \
-    }
 
 int launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
                   const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
                   float *pos_targets, hipStream_t stream) {
-    TG_FOR_EACH_MODEL(TG_IK_DLS)
-    return jit_launch_ik_dls(hash, root, dof, n, ch, K, goal_pos, goal_quat, lambda2, dq, err, pos_targets, stream);
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(ik_dls_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, n, ch, K, goal_pos, goal_quat,
+                 lambda2, dq, err, pos_targets);
+    }) ? rc : jit_launch_ik_dls(hash, root, dof, n, ch, K, goal_pos, goal_quat, lambda2, dq, err, pos_targets, stream);
 }
-
-#define TG_RB_FORCES(MODEL)                                                                              \
-    if (hash == MODEL::hash) {                                                                            \
-        hipLaunchKernelGGL(rb_force_kernel<MODEL>, dim3((n + COMPOSE_WPB - 1) / COMPOSE_WPB), dim3(64 * COMPOSE_WPB), \
-                           0, stream, root, dof, comp, n,                                                 \
-                           mass_scale, forces, torques, space, out, props);                               \
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                          \
-    }
 
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {
-    TG_FOR_EACH_MODEL(TG_RB_FORCES)
-    return jit_launch_rb_forces(hash, root, dof, comp, n, mass_scale, forces, torques, space, out, props, stream);
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(rb_force_kernel<decltype(m)>, dim3((n + COMPOSE_WPB - 1) / COMPOSE_WPB), dim3(64 * COMPOSE_WPB),
+                 stream, root, dof, comp, n, mass_scale, forces, torques, space, out, props);
+    }) ? rc : jit_launch_rb_forces(hash, root, dof, comp, n, mass_scale, forces, torques, space, out, props, stream);
 }
 
-int compiled_hashes(uint64_t *out, int cap) {
-    int n = 0;
-    TG_FOR_EACH_MODEL(TG_HASH)
-    return n;
-}
-#define TG_COMPOSE_ONLY(MODEL)                                                                            \
-    if (hash == MODEL::hash) {                                                                            \
-        hipLaunchKernelGGL(compose_kernel<MODEL>, dim3((a.N + COMPOSE_WPB - 1) / COMPOSE_WPB),            \
-                           dim3(64 * COMPOSE_WPB), 0, stream, a);                                         \
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;                                          \
-    }
 int launch_compose_only(uint64_t hash, const StepArgs &a, hipStream_t stream) {
-    TG_FOR_EACH_MODEL(TG_COMPOSE_ONLY)
-    return TG_ERR_MODEL;
-}
-#define TG_FUSED(MODEL) if (hash == MODEL::hash) return MODEL::FUSED;
-int model_fused(uint64_t hash) {
-    TG_FOR_EACH_MODEL(TG_FUSED)
-    return 0;
-}
-#define TG_EPB(MODEL) if (hash == MODEL::hash) return MODEL::EPB;
-int model_epb(uint64_t hash) {
-    TG_FOR_EACH_MODEL(TG_EPB)
-    return 0;
-}
-#define TG_TL(MODEL) if (hash == MODEL::hash) return MODEL::NTL;
-int model_tl(uint64_t hash) {
-    TG_FOR_EACH_MODEL(TG_TL)
-    return 0;
-}
-int model_kc(uint64_t hash) {
-    TG_FOR_EACH_MODEL(TG_KC)
-    return jit_kc(hash);
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(compose_kernel<decltype(m)>, dim3((a.N + COMPOSE_WPB - 1) / COMPOSE_WPB), dim3(64 * COMPOSE_WPB),
+                 stream, a);
+    }) ? rc : TG_ERR_MODEL;
 }
 
 }  // namespace tg

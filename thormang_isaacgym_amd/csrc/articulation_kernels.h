@@ -84,10 +84,6 @@ template <int NV> __device__ __forceinline__ void wave_sum_n(float *v) {
         for (int k = 0; k < NV; ++k) v[k] += __shfl_xor(v[k], m, 64);
 }
 
-// COMPOSE_WPB wavefronts per workgroup, one env each: a launch over all envs
-// is N / COMPOSE_WPB workgroups (most waves exit at once), not N
-constexpr int COMPOSE_WPB = 8;
-
 // Prologue (tg_walk_step): the walk task's pre_physics_step fused into the
 // compose launch that precedes every step kernel -- the same fp32 operations
 // as walk_task.hip walk_pre_kernel (no contraction: default + scale * a).
@@ -828,8 +824,7 @@ __device__ __forceinline__ void fk_root_relative(const float *r, const float *q,
 // out, 16 bytes per lane per store (a scalar head and tail where the chunk
 // does not start or end on a 16-byte line; the tile is kept congruent to the
 // global address mod 16 bytes, so the LDS reads are 16 bytes wide too).
-constexpr int JAC_THREADS = 256;
-constexpr int JAC_TILE = 4096;
+constexpr int JAC_TILE = 4096;   // (JAC_THREADS threads per env: tg_kernels.h)
 
 template <class M>
 __device__ __forceinline__ void jac_column(int l, int col, const float (*A)[3], const float (*T)[12],

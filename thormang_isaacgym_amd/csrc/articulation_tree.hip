@@ -15,29 +15,14 @@
 
 namespace tg {
 
-int tree_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
-    return unit_launch_step(hash, a, stream, ev_begin, ev_end);
+template <class P>
+int tree_launch(uint64_t hash, const StepArgs &a, const typename P::Args &pa, hipStream_t stream, hipEvent_t ev_begin,
+                hipEvent_t ev_end) {
+    return unit_launch<P>(hash, a, pa, stream, ev_begin, ev_end);
 }
-int tree_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
-                        hipEvent_t ev_end) {
-    return unit_launch_step_cf(hash, a, cf, stream, ev_begin, ev_end);
-}
-int tree_launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream,
-                        hipEvent_t ev_begin, hipEvent_t ev_end) {
-    return unit_launch_step_df(hash, a, cf, df, stream, ev_begin, ev_end);
-}
-int tree_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
-                            hipEvent_t ev_begin, hipEvent_t ev_end) {
-    return unit_launch_step_gogoro(hash, a, pa, stream, ev_begin, ev_end);
-}
-int tree_launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPostArgs &pa, hipStream_t stream,
-                          hipEvent_t ev_begin, hipEvent_t ev_end) {
-    return unit_launch_step_walk(hash, a, pa, stream, ev_begin, ev_end);
-}
-int tree_launch_step_paper(uint64_t hash, const StepArgs &a, const PaperPostArgs &pa, hipStream_t stream,
-                           hipEvent_t ev_begin, hipEvent_t ev_end) {
-    return unit_launch_step_paper(hash, a, pa, stream, ev_begin, ev_end);
-}
+#define TG_TREE_LAUNCH(P) \
+    template int tree_launch<P>(uint64_t, const StepArgs &, const P::Args &, hipStream_t, hipEvent_t, hipEvent_t);
+TG_FOR_EACH_POST(TG_TREE_LAUNCH)
 
 // developer builds: the section counters of this unit's step kernels
 // (articulation.hip's tg_prof_read / tg_cprof_read add them to its own)

@@ -34,8 +34,6 @@
 namespace tg {
 namespace {
 
-constexpr int JIT_COMPOSE_WPB = 8;   // articulation_kernels.h COMPOSE_WPB
-constexpr int JIT_JAC_THREADS = 256;   // articulation_kernels.h JAC_THREADS
 enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, NK };
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
@@ -280,8 +278,8 @@ int jit_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEve
     StepArgs aa = a;
     void *cargs[] = {&aa};
     if (!a.skip_compose)
-        if (int rc = launch(L->f[K_COMPOSE], (unsigned)((a.N + JIT_COMPOSE_WPB - 1) / JIT_COMPOSE_WPB),
-                            64 * JIT_COMPOSE_WPB, 0, stream, cargs))
+        if (int rc = launch(L->f[K_COMPOSE], (unsigned)((a.N + COMPOSE_WPB - 1) / COMPOSE_WPB),
+                            64 * COMPOSE_WPB, 0, stream, cargs))
             return rc;
     if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
     char pa = 0;   // the step kernel's empty NoPost::Args
@@ -307,7 +305,7 @@ int jit_launch_rb_forces(uint64_t hash, const float *root, const float *dof, con
     JitLoaded *L = find(hash);
     if (!L) return TG_ERR_MODEL;
     void *args[] = {&root, &dof, &comp, &n, &mass_scale, &forces, &torques, &space, &out, &props};
-    return launch(L->f[K_RBF], (unsigned)((n + JIT_COMPOSE_WPB - 1) / JIT_COMPOSE_WPB), 64 * JIT_COMPOSE_WPB, 0, stream,
+    return launch(L->f[K_RBF], (unsigned)((n + COMPOSE_WPB - 1) / COMPOSE_WPB), 64 * COMPOSE_WPB, 0, stream,
                   args);
 }
 
@@ -315,7 +313,7 @@ int jit_launch_jacobians(uint64_t hash, const float *root, const float *dof, int
     JitLoaded *L = find(hash);
     if (!L) return TG_ERR_MODEL;
     void *args[] = {&root, &dof, &n, &out};
-    return launch(L->f[K_JAC], (unsigned)n, JIT_JAC_THREADS, 0, stream, args);
+    return launch(L->f[K_JAC], (unsigned)n, JAC_THREADS, 0, stream, args);
 }
 
 int jit_launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,

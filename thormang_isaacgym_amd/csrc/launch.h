@@ -6,6 +6,7 @@
 // (build_ext.py): each model's step kernel is instantiated in exactly one of
 // them, chosen by TG_UNIT_TREE.
 #pragma once
+#include <type_traits>
 
 namespace tg {
 
@@ -40,8 +41,8 @@ template <class M> void launch_compose(const StepArgs &a, hipStream_t stream) {
 
 // HF: terrain heightfield present (tg_set_heightfield); the flat-ground
 // instantiation keeps the contact normal a compile-time e_z.
-template <class M, bool HF, class P = NoPost>
-int launch_par(const StepArgs &a, hipStream_t stream, const typename P::Args &pa = {}) {
+template <class M, bool HF, class P>
+int launch_par(const StepArgs &a, hipStream_t stream, const typename P::Args &pa) {
     constexpr size_t bytes = ParLayout<M>::template bytes<M::EPB>();
     static_assert(bytes <= 160 * 1024, "LDS budget");
     // the dynamic-LDS attribute is per device: one bit per device of this
@@ -62,111 +63,76 @@ int launch_par(const StepArgs &a, hipStream_t stream, const typename P::Args &pa
     return 0;
 }
 
-template <class M> int launch_model(const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
-    if constexpr (!in_unit<M>()) {
-        return TG_OTHER_UNIT;
-    } else {
-    launch_compose<M>(a, stream);
-    if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
-    if (int rc = a.hf ? launch_par<M, true>(a, stream) : launch_par<M, false>(a, stream)) return rc;
-    if (ev_end && hipEventRecord(ev_end, stream) != hipSuccess) return TG_ERR_HIP;
-    return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
-    }
-}
-
-// the step with the net contact force export (NoPostCF, cf [N, NL, 3]):
-// instantiated beside the plain pair for every model with contact rows; a
-// model without any has nothing to export and runs the plain kernel (the
-// tensor keeps the zeros it was enabled with)
-template <class M>
-int launch_model_cf(const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end) {
-    if constexpr (!in_unit<M>()) {
-        return TG_OTHER_UNIT;
-    } else if constexpr (M::NROWS == 0) {
-        return launch_model<M>(a, stream, ev_begin, ev_end);
-    } else {
-        launch_compose<M>(a, stream);
-        if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
-        const NoPostCF::Args pa{cf};
-        if (int rc = a.hf ? launch_par<M, true, NoPostCF>(a, stream, pa) : launch_par<M, false, NoPostCF>(a, stream, pa))
-            return rc;
-        if (ev_end && hipEventRecord(ev_end, stream) != hipSuccess) return TG_ERR_HIP;
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
-    }
-}
-
-// the step with the DOF force export (NoPostDF, df [N, ND]) and, when cf is
-// not null, the net contact force export too: one more pair per model, with
-// or without contact rows (a model without any has no contact part)
-template <class M>
-int launch_model_df(const StepArgs &a, float *cf, float *df, hipStream_t stream, hipEvent_t ev_begin,
-                    hipEvent_t ev_end) {
-    if constexpr (!in_unit<M>()) {
-        return TG_OTHER_UNIT;
-    } else {
-        launch_compose<M>(a, stream);
-        if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
-        const NoPostDF::Args pa{cf, df};
-        if (int rc = a.hf ? launch_par<M, true, NoPostDF>(a, stream, pa) : launch_par<M, false, NoPostDF>(a, stream, pa))
-            return rc;
-        if (ev_end && hipEventRecord(ev_end, stream) != hipSuccess) return TG_ERR_HIP;
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
-    }
-}
-
+// What differs between the variants of the step kernel at launch, per post
+// policy P: which models have the instantiation (eligible), whether the
+// terrain one exists beside the flat-ground one (HF), what a model without it
+// runs instead (Fallback; void: nothing, the call is declined with 1), and the
+// run-time test of a call (accepts; false: declined with 1, nothing launched).
+struct AnyStep {
+    template <class M> static constexpr bool eligible = true;
+    static constexpr bool HF = true;
+    using Fallback = void;
+    template <class M, class A> static bool accepts(const StepArgs &, const A &) { return true; }
+};
+// the plain step, and the DOF force export (NoPostDF, df [N, ND]; with the
+// net contact force export too when its cf is not null): one more pair per
+// model, with or without contact rows (a model without any has no contact part)
+template <class P> struct StepVariant : AnyStep {};
+// the net contact force export (NoPostCF, cf [N, NL, 3]): instantiated beside
+// the plain pair for every model with contact rows; a model without any has
+// nothing to export and runs the plain kernel (the tensor keeps the zeros it
+// was enabled with)
+template <> struct StepVariant<NoPostCF> : AnyStep {
+    template <class M> static constexpr bool eligible = M::NROWS > 0;
+    using Fallback = NoPost;
+};
 // the fused walk epilogue is instantiated for the lane-pair (humanoid-size)
 // trees on flat ground only
-template <class M>
-int launch_model_walk(const StepArgs &a, const WalkPostArgs &pa, hipStream_t stream, hipEvent_t ev_begin,
-                      hipEvent_t ev_end) {
-    if constexpr (!in_unit<M>()) {
-        return TG_OTHER_UNIT;
-    } else if constexpr (M::PAIR == 0 || M::ND > 64) {
-        return 1;
-    } else {
-        if (a.hf || pa.p.num_dof != M::ND) return 1;
-        launch_compose<M>(a, stream);
-        if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
-        if (int rc = launch_par<M, false, WalkPost>(a, stream, pa)) return rc;
-        if (ev_end && hipEventRecord(ev_end, stream) != hipSuccess) return TG_ERR_HIP;
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
+template <> struct StepVariant<WalkPost> : AnyStep {
+    template <class M> static constexpr bool eligible = M::PAIR != 0 && M::ND <= 64;
+    static constexpr bool HF = false;
+    template <class M> static bool accepts(const StepArgs &a, const WalkPostArgs &pa) {
+        return !a.hf && pa.p.num_dof == M::ND;
     }
-}
-
+};
 // the fused Gogoro epilogue is instantiated for the registered task's model
 // (codegen FUSED bit 1), flat ground and terrain
-template <class M>
-int launch_model_gogoro(const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream, hipEvent_t ev_begin,
-                        hipEvent_t ev_end) {
-    if constexpr (!in_unit<M>()) {
-        return TG_OTHER_UNIT;
-    } else if constexpr ((M::FUSED & 2) == 0) {
-        return 1;
-    } else {
-        if (pa.p.num_dof != M::ND) return 1;
-        launch_compose<M>(a, stream);
-        if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
-        if (int rc = a.hf ? launch_par<M, true, GogoroPost>(a, stream, pa) : launch_par<M, false, GogoroPost>(a, stream, pa))
-            return rc;
-        if (ev_end && hipEventRecord(ev_end, stream) != hipSuccess) return TG_ERR_HIP;
-        return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
+template <> struct StepVariant<GogoroPost> : AnyStep {
+    template <class M> static constexpr bool eligible = (M::FUSED & 2) != 0;
+    template <class M> static bool accepts(const StepArgs &, const GogoroPostArgs &pa) {
+        return pa.p.num_dof == M::ND;
     }
-}
-
+};
 // the fused GogoroPaper epilogue (one launch per step): the paper model with
 // in-place seat composites (codegen FUSED bit 4), flat ground
-template <class M>
-int launch_model_paper(const StepArgs &a, const PaperPostArgs &pa, hipStream_t stream, hipEvent_t ev_begin,
-                       hipEvent_t ev_end) {
+template <> struct StepVariant<PaperPost> : AnyStep {
+    template <class M>
+    static constexpr bool eligible = (M::FUSED & 4) != 0 && M::NTL > 0 && M::LCOM && M::NG <= M::LPE && M::LPE >= 8;
+    static constexpr bool HF = false;
+    template <class M> static bool accepts(const StepArgs &a, const PaperPostArgs &pa) {
+        return !a.hf && pa.p.num_dof == M::ND && a.N % M::EPB == 0;
+    }
+};
+
+// compose, then model M's step kernel with post policy P; ev_begin / ev_end
+// (optional) are recorded around the step kernel itself
+template <class M, class P>
+int launch_model(const StepArgs &a, const typename P::Args &pa, hipStream_t stream, hipEvent_t ev_begin,
+                 hipEvent_t ev_end) {
+    using V = StepVariant<P>;
     if constexpr (!in_unit<M>()) {
         return TG_OTHER_UNIT;
-    } else if constexpr ((M::FUSED & 4) == 0 || M::NTL == 0 || !M::LCOM || M::NG > M::LPE || M::LPE < 8) {
-        return 1;
+    } else if constexpr (!V::template eligible<M>) {
+        if constexpr (std::is_void_v<typename V::Fallback>) return 1;
+        else return launch_model<M, typename V::Fallback>(a, {}, stream, ev_begin, ev_end);
     } else {
-        if (a.hf || pa.p.num_dof != M::ND || a.N % M::EPB != 0) return 1;
+        if (!V::template accepts<M>(a, pa)) return 1;
         launch_compose<M>(a, stream);
         if (ev_begin && hipEventRecord(ev_begin, stream) != hipSuccess) return TG_ERR_HIP;
-        if (int rc = launch_par<M, false, PaperPost>(a, stream, pa)) return rc;
+        int rc;
+        if constexpr (V::HF) rc = a.hf ? launch_par<M, true, P>(a, stream, pa) : launch_par<M, false, P>(a, stream, pa);
+        else rc = launch_par<M, false, P>(a, stream, pa);
+        if (rc) return rc;
         if (ev_end && hipEventRecord(ev_end, stream) != hipSuccess) return TG_ERR_HIP;
         return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
     }
@@ -174,59 +140,20 @@ int launch_model_paper(const StepArgs &a, const PaperPostArgs &pa, hipStream_t s
 
 // this unit's dispatch (TG_OTHER_UNIT: a model this unit does not instantiate)
 #define TG_U_LAUNCH(MODEL) \
-    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model<MODEL>(a, stream, ev_begin, ev_end);
-#define TG_U_LAUNCH_GOGORO(MODEL) \
-    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model_gogoro<MODEL>(a, pa, stream, ev_begin, ev_end);
-#define TG_U_LAUNCH_WALK(MODEL) \
-    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model_walk<MODEL>(a, pa, stream, ev_begin, ev_end);
-static int unit_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin,
-                            hipEvent_t ev_end) {
+    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model<MODEL, P>(a, pa, stream, ev_begin, ev_end);
+template <class P>
+static int unit_launch(uint64_t hash, const StepArgs &a, const typename P::Args &pa, hipStream_t stream,
+                       hipEvent_t ev_begin, hipEvent_t ev_end) {
     TG_FOR_EACH_MODEL(TG_U_LAUNCH)
     return TG_OTHER_UNIT;
 }
-#define TG_U_LAUNCH_CF(MODEL) \
-    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model_cf<MODEL>(a, cf, stream, ev_begin, ev_end);
-static int unit_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
-                               hipEvent_t ev_end) {
-    TG_FOR_EACH_MODEL(TG_U_LAUNCH_CF)
-    return TG_OTHER_UNIT;
-}
-#define TG_U_LAUNCH_DF(MODEL) \
-    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model_df<MODEL>(a, cf, df, stream, ev_begin, ev_end);
-static int unit_launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream,
-                               hipEvent_t ev_begin, hipEvent_t ev_end) {
-    TG_FOR_EACH_MODEL(TG_U_LAUNCH_DF)
-    return TG_OTHER_UNIT;
-}
-static int unit_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
-                                   hipEvent_t ev_begin, hipEvent_t ev_end) {
-    TG_FOR_EACH_MODEL(TG_U_LAUNCH_GOGORO)
-    return TG_OTHER_UNIT;
-}
-#define TG_U_LAUNCH_PAPER(MODEL) \
-    if (in_unit<MODEL>() && hash == MODEL::hash) return launch_model_paper<MODEL>(a, pa, stream, ev_begin, ev_end);
-static int unit_launch_step_paper(uint64_t hash, const StepArgs &a, const PaperPostArgs &pa, hipStream_t stream,
-                                  hipEvent_t ev_begin, hipEvent_t ev_end) {
-    TG_FOR_EACH_MODEL(TG_U_LAUNCH_PAPER)
-    return TG_OTHER_UNIT;
-}
-static int unit_launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPostArgs &pa, hipStream_t stream,
-                                 hipEvent_t ev_begin, hipEvent_t ev_end) {
-    TG_FOR_EACH_MODEL(TG_U_LAUNCH_WALK)
-    return TG_OTHER_UNIT;
-}
+#undef TG_U_LAUNCH
 
-// the humanoid unit's entries (articulation_tree.hip)
-int tree_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end);
-int tree_launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin,
-                        hipEvent_t ev_end);
-int tree_launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream,
-                        hipEvent_t ev_begin, hipEvent_t ev_end);
-int tree_launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
-                            hipEvent_t ev_begin, hipEvent_t ev_end);
-int tree_launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPostArgs &pa, hipStream_t stream,
-                          hipEvent_t ev_begin, hipEvent_t ev_end);
-int tree_launch_step_paper(uint64_t hash, const StepArgs &a, const PaperPostArgs &pa, hipStream_t stream,
-                           hipEvent_t ev_begin, hipEvent_t ev_end);
+// the humanoid unit's entry (articulation_tree.hip instantiates it for every
+// post policy of the list)
+#define TG_FOR_EACH_POST(X) X(NoPost) X(NoPostCF) X(NoPostDF) X(WalkPost) X(GogoroPost) X(PaperPost)
+template <class P>
+int tree_launch(uint64_t hash, const StepArgs &a, const typename P::Args &pa, hipStream_t stream, hipEvent_t ev_begin,
+                hipEvent_t ev_end);
 
 }  // namespace tg

@@ -156,33 +156,34 @@ struct PaperPostArgs {
     unsigned t7_target;
     int nblk;              // term-7 blocks (workgroups) of this launch
 };
-#ifndef __HIPCC_RTC__   // host launchers (not part of a hipRTC unit, jit.cpp)
-// compose + step kernel with the GogoroPaper post-physics fused in; returns 1
-// when the model has no such instantiation
-int launch_step_paper(uint64_t hash, const StepArgs &a, const PaperPostArgs &pa, hipStream_t stream,
-                      hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
-// compose + step kernel with the Gogoro post-physics fused in; returns 1 when
-// the model has no such instantiation
-int launch_step_gogoro(uint64_t hash, const StepArgs &a, const GogoroPostArgs &pa, hipStream_t stream,
-                       hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
-// compose + step kernel with the walk post-physics fused in; returns 1 (nothing
-// launched) when the model / ground has no fused instantiation
-int launch_step_walk(uint64_t hash, const StepArgs &a, const WalkPostArgs &pa, hipStream_t stream,
-                     hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 
-// ev_begin / ev_end (optional) are recorded around the step kernel itself
-int launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin = nullptr,
-                hipEvent_t ev_end = nullptr);
-// launch_step with the net contact force export (step_par.h NoPostCF): cf
-// [N, L, 3] is written for every link that carries a shape.  Compiled-in
+// launch figures that the kernels (articulation_kernels.h) and both host
+// launch paths (articulation.hip, jit.cpp) share
+// COMPOSE_WPB wavefronts per workgroup, one env each: a launch over all envs
+// is N / COMPOSE_WPB workgroups (most waves exit at once), not N
+constexpr int COMPOSE_WPB = 8;
+constexpr int JAC_THREADS = 256;   // threads per env of jacobian_kernel
+
+#ifndef __HIPCC_RTC__   // host launchers (not part of a hipRTC unit, jit.cpp)
+// what rides on a step: one fused task epilogue (post-physics in the step
+// kernel) at the most, or the force exports -- cf [N, L, 3], the net contact
+// force of every link that carries a shape (step_par.h NoPostCF), and df
+// [N, D], the DOF forces, written in full (NoPostDF, which exports cf too when
+// it is set).  The exports have no fused-epilogue variant.
+struct StepPost {
+    const WalkPostArgs *walk = nullptr;
+    const GogoroPostArgs *gogoro = nullptr;
+    const PaperPostArgs *paper = nullptr;
+    float *cf = nullptr, *df = nullptr;
+    bool fused() const { return walk || gogoro || paper; }
+};
+// compose + the step kernel that carries post; ev_begin / ev_end (optional)
+// are recorded around the step kernel itself.  A fused epilogue returns 1
+// (nothing launched) when the model / ground / batch has no such
+// instantiation, run-time models included; the exports are for compiled-in
 // models only (TG_ERR_MODEL otherwise)
-int launch_step_cf(uint64_t hash, const StepArgs &a, float *cf, hipStream_t stream, hipEvent_t ev_begin = nullptr,
-                   hipEvent_t ev_end = nullptr);
-// launch_step with the DOF force export (step_par.h NoPostDF): df [N, D] is
-// written in full; cf as in launch_step_cf, or null for no contact export.
-// Compiled-in models only (TG_ERR_MODEL otherwise)
-int launch_step_df(uint64_t hash, const StepArgs &a, float *cf, float *df, hipStream_t stream,
-                   hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
+int launch_step(uint64_t hash, const StepArgs &a, const StepPost &post, hipStream_t stream,
+                hipEvent_t ev_begin = nullptr, hipEvent_t ev_end = nullptr);
 int compiled_hashes(uint64_t *out, int cap);
 int launch_body_states(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
 // Jacobians [N,L,6,6+D] (jacobian_kernel) and mass matrices [N,6+D,6+D]
@@ -198,11 +199,16 @@ int launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, con
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream);
-int model_kc(uint64_t hash);
-int model_tl(uint64_t hash);
-int model_epb(uint64_t hash);   // envs per step-kernel workgroup of a compiled model (0: not compiled in)
-int model_fused(uint64_t hash);   // codegen FUSED bits of a compiled model (0: none / not compiled in)
-int launch_compose_only(uint64_t hash, const StepArgs &a, hipStream_t stream);   // every dirty env, no step   // translating locks of a compiled model (codegen translating_locks), 0 otherwise
+// the codegen figures of a compiled-in model (as initialised: not compiled in;
+// jit_kc has a run-time model's kc)
+struct ModelInfo {
+    int kc = -1;     // per-env composite floats
+    int tl = 0;      // translating locks (codegen translating_locks)
+    int epb = 0;     // envs per step-kernel workgroup
+    int fused = 0;   // codegen FUSED bits
+};
+ModelInfo model_info(uint64_t hash);
+int launch_compose_only(uint64_t hash, const StepArgs &a, hipStream_t stream);   // every dirty env, no step
 
 // run-time compiled models (jit.cpp, tg_model_jit): the launchers above fall
 // through to these when no compiled-in specialisation matches the hash

@@ -215,7 +215,7 @@ uint64_t tg_compiled_model_hashes(uint64_t *out, int32_t cap) { return (uint64_t
 int tg_model_jit(uint64_t model_hash, const char *struct_name, const char *model_source, const char *include_dir,
                  const char *cache_dir) {
     if (!struct_name || !model_source) return fail(TG_ERR_ARG, "tg_model_jit: null argument");
-    if (tg::model_kc(model_hash) >= 0 && !tg::jit_has(model_hash)) return TG_OK;   // compiled in
+    if (tg::model_info(model_hash).kc >= 0 && !tg::jit_has(model_hash)) return TG_OK;   // compiled in
     std::string err;
     if (int rc = tg::jit_compile(model_hash, struct_name, model_source, include_dir, cache_dir, err))
         return fail(rc, "tg_model_jit(0x%016llx): %s", (unsigned long long)model_hash, err.c_str());
@@ -232,7 +232,8 @@ int tg_sim_create(const tg_model_desc *m, const tg_sim_params *params, int32_t n
         return fail(TG_ERR_ARG, "contact / velocity iterations must be >= 0");
     if (params->solver_type != 0 && params->solver_type != 1)
         return fail(TG_ERR_ARG, "solver_type must be 0 (PGS) or 1 (TGS), got %d", params->solver_type);
-    int kc = tg::model_kc(m->model_hash);
+    int kc = tg::model_info(m->model_hash).kc;
+    if (kc < 0) kc = tg::jit_kc(m->model_hash);   // a run-time model
     if (kc < 0)
         return fail(TG_ERR_MODEL,
                     "model hash 0x%016llx has no specialisation in libtgsim.so: compiled-in models are listed by "
@@ -254,7 +255,7 @@ int tg_sim_create(const tg_model_desc *m, const tg_sim_params *params, int32_t n
     if (const char *u = getenv("TG_PAPER_TWO_LAUNCH")) s->paper_two_launch = u[0] == '1';
     // (TG_NO_SHARED_CACHE=1: every env reads its own block, the A/B control)
     const char *nsc = getenv("TG_NO_SHARED_CACHE");
-    s->uni_ok = !(nsc && nsc[0] == '1') && (tg::model_fused(m->model_hash) & 6) == 0 && !tg::jit_has(m->model_hash);
+    s->uni_ok = !(nsc && nsc[0] == '1') && (tg::model_info(m->model_hash).fused & 6) == 0 && !tg::jit_has(m->model_hash);
     s->device = device;
     s->N = num_envs;
     s->D = m->num_dofs;
@@ -508,8 +509,8 @@ int tg_set_heightfield(tg_sim *s, const float *heights, int32_t rows, int32_t co
 }
 
 // compose (+ optional prologue in a) and the step kernel of one simulate call;
-// with wp, the step kernel carrying the walk post-physics epilogue (returns 1,
-// nothing launched, when the model has no such instantiation)
+// with a fused epilogue in post, the step kernel carrying that post-physics
+// (returns 1, nothing launched, when the model has no such instantiation)
 // makes the sim's device current for the launches of one call (per-device
 // kernel attributes, tg_set_stream's stream), restoring the caller's device
 struct DeviceGuard {
@@ -523,12 +524,13 @@ struct DeviceGuard {
     }
 };
 
-static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, const tg::WalkPostArgs *wp = nullptr,
-                         const tg::GogoroPostArgs *gp = nullptr, const tg::PaperPostArgs *pp = nullptr) {
+static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, tg::StepPost post = {}) {
     // the net contact force and DOF force exports have no fused-epilogue
     // variant: the task steps take their general path (simulates, then the
     // post-physics launch)
-    if ((s->cf || s->df) && (wp || gp || pp)) return 1;
+    if ((s->cf || s->df) && post.fused()) return 1;
+    post.cf = s->cf;
+    post.df = s->df;
     DeviceGuard dg(s->device);
     tg::StepArgs a = a_in;
     // the compose launch: every dirty env (host-side changes possible), the
@@ -594,12 +596,7 @@ static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, const tg::WalkPost
             HIPCHK(hipEventCreate(&ev.second));
         }
     }
-    int rc = wp   ? tg::launch_step_walk(s->hash, a, *wp, s->stream, ev.first, ev.second)
-             : gp ? tg::launch_step_gogoro(s->hash, a, *gp, s->stream, ev.first, ev.second)
-             : pp ? tg::launch_step_paper(s->hash, a, *pp, s->stream, ev.first, ev.second)
-             : s->df ? tg::launch_step_df(s->hash, a, s->cf, s->df, s->stream, ev.first, ev.second)
-             : s->cf ? tg::launch_step_cf(s->hash, a, s->cf, s->stream, ev.first, ev.second)
-                     : tg::launch_step(s->hash, a, s->stream, ev.first, ev.second);
+    const int rc = tg::launch_step(s->hash, a, post, s->stream, ev.first, ev.second);
     // the pair joins the pending list only once both events were recorded by a
     // launch that went through; otherwise it goes back to the free list
     if (rc != 0) {
@@ -633,8 +630,8 @@ static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, const tg::WalkPost
         if (!a.compose_list) s->dirty_possible = false;
         s->list_pending = false;
     }
-    if (gp && !gp->tl_inplace) {   // the Gogoro epilogue's resets rewrite properties
-        if (gp->reset_list) {       // ... and are listed for the next compose
+    if (post.gogoro && !post.gogoro->tl_inplace) {   // the Gogoro epilogue's resets rewrite properties
+        if (post.gogoro->reset_list) {                // ... and are listed for the next compose
             s->list_pending = true;
             s->list_cur = 1 - s->list_cur;
         } else {
@@ -938,14 +935,16 @@ int tg_gogoro_step(tg_sim *s, const tg_gogoro_params *p, const tg_gogoro_buffers
         if (i == n_simulate - 1 && !s->post_unfused) {   // post-physics fused into the last step kernel
             // models whose resets only move translating locks (the seat chain)
             // update their composites in the epilogue; others list their resets
-            const bool inplace = tg::model_tl(s->hash) > 0 && !s->no_inplace;
+            const bool inplace = tg::model_info(s->hash).tl > 0 && !s->no_inplace;
             const tg::GogoroPostArgs gp{*p, *b, (uint32_t)counter_post, (uint32_t)(counter_post >> 32),
                                         inplace ? nullptr : s->clist + (size_t)s->list_cur * s->N,
                                         inplace ? nullptr : s->ccount + s->list_cur, inplace ? 1 : 0,
                                         reset_draws, obs_draws, speed_draws, yaw_draws};
             // one launch: the pre-physics too runs in the step kernel
             a.gp_in_step = (n_simulate == 1 && !s->pre_in_compose) ? 1 : 0;
-            const int rc = simulate_args(s, a, nullptr, &gp);
+            tg::StepPost post;
+            post.gogoro = &gp;
+            const int rc = simulate_args(s, a, post);
             if (rc == 0) return TG_OK;
             if (rc < 0) return rc;
             a.gp_in_step = 0;   // no fused instantiation: the prologue rides in compose
@@ -1031,7 +1030,9 @@ int tg_walk_step(tg_sim *s, const tg_walk_params *p, const tg_walk_buffers *b, c
         for (int d = 0; d < p->num_dof; ++d) a.pm_default[d] = p->default_pos[d];
         a.pm_in_step = 1;
         const tg::WalkPostArgs wp{*p, *b, reset_draws, push_draws, (uint32_t)counter, (uint32_t)(counter >> 32)};
-        const int rc = simulate_args(s, a, &wp);
+        tg::StepPost post;
+        post.walk = &wp;
+        const int rc = simulate_args(s, a, post);
         if (rc <= 0) return rc;
         // rc == 1: no fused instantiation for this model / ground -- the general path below
     }
@@ -1047,7 +1048,9 @@ int tg_walk_step(tg_sim *s, const tg_walk_params *p, const tg_walk_buffers *b, c
         }
         if (i == n_simulate - 1 && !s->walk_unfused) {   // post-physics fused into the last step kernel
             const tg::WalkPostArgs wp{*p, *b, reset_draws, push_draws, (uint32_t)counter, (uint32_t)(counter >> 32)};
-            const int rc = simulate_args(s, a, &wp);
+            tg::StepPost post;
+            post.walk = &wp;
+            const int rc = simulate_args(s, a, post);
             if (rc == 0) return TG_OK;
             if (rc < 0) return rc;
         }
@@ -1129,9 +1132,9 @@ static tg::PaperPre paper_pre_args(const tg_paper_params *p, const tg_paper_buff
 static int paper_one_launch(tg_sim *s, const tg_paper_params *p, const tg_paper_buffers *b, const float *actions,
                             uint64_t counter) {
     if (s->paper_two_launch || s->pre_in_compose || s->paper_finish_launch || s->no_inplace || s->hf_rows > 0 ||
-        (b->rb_forces && s->paper_rb_launch) || !(tg::model_fused(s->hash) & 4) || tg::model_tl(s->hash) <= 0)
+        (b->rb_forces && s->paper_rb_launch) || !(tg::model_info(s->hash).fused & 4) || tg::model_info(s->hash).tl <= 0)
         return 1;
-    const int epb = tg::model_epb(s->hash);
+    const int epb = tg::model_info(s->hash).epb;
     if (epb != TG_PAPER_T7_BLK || s->N % epb != 0) return 1;
     if (s->num_cus == 0) {
         DeviceGuard dg(s->device);
@@ -1153,7 +1156,9 @@ static int paper_one_launch(tg_sim *s, const tg_paper_params *p, const tg_paper_
     const bool rb = b->rb_forces != nullptr;
     const tg::PaperPostArgs pa{*p, *b, (uint32_t)counter, (uint32_t)(counter >> 32), rb ? s->force : nullptr,
                                s->t7cnt, s->t7_total + (unsigned)nblk, nblk};
-    if (int rc = simulate_args(s, a, nullptr, nullptr, &pa)) return rc < 0 ? rc : 1;
+    tg::StepPost post;
+    post.paper = &pa;
+    if (int rc = simulate_args(s, a, post)) return rc < 0 ? rc : 1;
     s->t7_total += (unsigned)nblk;   // (the launch adds nblk arrivals)
     if (rb) {   // the next simulate's rigid-body forces, reduced already
         s->rbf_f = b->rb_forces;
@@ -1196,7 +1201,7 @@ int tg_paper_step(tg_sim *s, const tg_paper_params *p, const tg_paper_buffers *b
             q.actions = actions;
             // (FUSED bit 4: the bit the step kernel tests before it runs the
             // paper pre-physics and forms the term-7 partials)
-            a.pp_in_step = (n_simulate == 1 && (tg::model_fused(s->hash) & 4) && !s->pre_in_compose) ? 1 : 0;
+            a.pp_in_step = (n_simulate == 1 && (tg::model_info(s->hash).fused & 4) && !s->pre_in_compose) ? 1 : 0;
             // the step kernel also forms reward term 7's partials, so the post
             // launch finishes the batch itself (no finish launch)
             if (a.pp_in_step && !s->paper_finish_launch && p->num_envs % 8 == 0) {   // 8: PAPER_EPW
