@@ -59,6 +59,10 @@
  *                            (tasks/gogoro/gogoro.py:381-427, with
  *                            orientation_error :605-608; the one-block control
  *                            of tasks/franka_cube_stack.py:392,602-628)
+ *   tg_osc                   _compute_osc_torques, operational-space control on
+ *                            one link's Jacobian block and the chain's block of
+ *                            the mass matrix, clamped to the effort limits
+ *                            (tasks/franka_cube_stack.py:602-628)
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -411,6 +415,77 @@ int tg_ik_dls(tg_sim *sim, const tg_ik_chain *chains /* HOST */, int32_t num_cha
               float *dq,               /* [N, K, TG_IK_MAX_DOFS] device or NULL */
               float *err,              /* [N, K, 6] device or NULL */
               float *pos_targets);     /* [N, D] device or NULL */
+/* Operational-space control, _compute_osc_torques of
+ * tasks/franka_cube_stack.py:602-628 in one kernel: for K chains per env, the
+ * joint torques
+ *   tau = J^T Lambda (kp err - kd v) + (H_c a - J^T Lambda (J a)),
+ *   Lambda = (J H_c^-1 J^T + lambda^2 I)^-1,
+ * on the chain's own Jacobian columns and the chain's own block of the mass
+ * matrix, and optionally their clamped sum into an actuation tensor.  On
+ * demand, stream-ordered, computed from the current root and dof state, the
+ * env's body mass scales and its TG_PROP_ARMATURE and TG_PROP_EFFORT rows;
+ * nothing of the sim is written.  The chains array and the gains are HOST
+ * memory, read during the call and not retained.  The chains are tg_ik_dls's
+ * tg_ik_chain records.  Chain k of env e has nd = num_dofs columns and R = 6
+ * rows, or R = 3 (the position rows) with goal_quat NULL.
+ *
+ * J (R x nd), the controlled point x and err are exactly tg_ik_dls's: the
+ * point is x = o_l + R_l offset on the link ORIGIN, the base is held fixed, a
+ * chain DOF whose joint is off the link's path has an exactly-0 column, a
+ * locked DOF is an ordinary column at its dof_state position, q_goal is
+ * normalised by the kernel, and err[3:6] is written as 0 without goal_quat.
+ *
+ * H_c (nd x nd) = H[6 + dofs[i], 6 + dofs[j]] with H as tg_mass_matrices
+ * defines it: the env's body mass scale and its TG_PROP_ARMATURE row included,
+ * locked DOFs ordinary rows.  It is the reference's mm[:, :7, :7], the inertia
+ * seen with the base and every non-chain joint held.
+ *
+ * v = J qd_c, qd_c the chain DOFs' dof_state velocities: the velocity of the
+ * controlled point with the base held, whatever the root's own velocity is.
+ * With a fixed base it equals the reference's eef_vel.
+ *
+ * Lambda = (J H_c^-1 J^T + lambda^2 I)^-1, lambda = gains.damping > 0, both
+ * inverses by Cholesky (H_c is SPD, and so is the R x R matrix since lambda >
+ * 0); the reference is lambda = 0.
+ *
+ * Null space, with q_rest only: a = kp_null w(q_rest - q) - kd_null qd over
+ * the chain's DOFs, w(x) = x - 2 pi floor((x + pi) / (2 pi)) for a revolute
+ * DOF (the reference's % (2 pi) wrap) and w(x) = x for a prismatic one;
+ * tau += H_c a - J^T Lambda (J a).  This is the reference's
+ * (I - J^T Jbar) H a with Jbar = Lambda J H_c^-1, identical for any lambda.
+ * kp_null and kd_null are ignored without q_rest.
+ *
+ * tau[e, k, c] is the torque of chain k's column c and exactly 0.0 for the
+ * padding c >= num_dofs: every element of tau and err is written.  Without
+ * q_rest an off-path column's tau is exactly 0.0.  tau is not clamped.
+ *
+ * efforts: for every DOF d that appears in at least one chain, efforts[e, d] =
+ * clamp(sum of tau[e, k, c] over all (k, c) with dofs[c] == d, in ascending
+ * (k, c) order, no atomics; -TG_PROP_EFFORT[e, d], +TG_PROP_EFFORT[e, d]), the
+ * reference's tensor_clamp to the effort limits; chains may share a DOF.  No
+ * other element of efforts is touched.  Passing the sim's live dof_actuation
+ * tensor (tg_state_view) is the intended use: the next tg_simulate applies it
+ * to the chain DOFs that are in EFFORT mode.
+ *
+ * TG_ERR_ARG (message "tg_osc: ...") for every chain error tg_ik_dls reports
+ * (null chains or goal_pos, num_chains outside 1..TG_IK_MAX_CHAINS, a link
+ * outside [0, L), num_dofs outside 1..TG_IK_MAX_DOFS, a DOF outside [0, D), a
+ * DOF twice in one chain), null gains, damping not > 0 or not finite, kp, kd,
+ * kp_null or kd_null negative or not finite, or tau, err and efforts all NULL.
+ * Every model, run-time (tg_model_jit) ones included. */
+typedef struct tg_osc_gains {      /* HOST, read during the call, one set for all chains */
+    float kp, kd;                  /* task space (reference: 150, 2 sqrt(kp)) */
+    float kp_null, kd_null;        /* null space (reference: 10, 2 sqrt(kp_null)); ignored without q_rest */
+    float damping;                 /* lambda > 0, regularises the task-space inertia */
+} tg_osc_gains;                    /* 20 bytes */
+int tg_osc(tg_sim *sim, const tg_ik_chain *chains /* HOST */, int32_t num_chains,
+           const float *goal_pos,   /* [N, K, 3] device, world */
+           const float *goal_quat,  /* [N, K, 4] xyzw device or NULL: 3 position rows only */
+           const float *q_rest,     /* [N, D] device or NULL: no null-space term */
+           const tg_osc_gains *gains,
+           float *tau,              /* [N, K, TG_IK_MAX_DOFS] device or NULL */
+           float *err,              /* [N, K, 6] device or NULL */
+           float *efforts);         /* [N, D] device or NULL */
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

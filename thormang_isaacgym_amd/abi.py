@@ -69,6 +69,12 @@ class tg_ik_chain(C.Structure):
     ]
 
 
+class tg_osc_gains(C.Structure):
+    """The gains of tg_osc (tgsim.h): task-space kp / kd, null-space kp_null / kd_null, the damping lambda."""
+    _fields_ = [("kp", C.c_float), ("kd", C.c_float), ("kp_null", C.c_float), ("kd_null", C.c_float),
+                ("damping", C.c_float)]
+
+
 F2 = C.c_float * 2
 
 

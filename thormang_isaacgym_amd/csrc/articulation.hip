@@ -158,6 +158,17 @@ int launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, con
     }) ? rc : jit_launch_ik_dls(hash, root, dof, n, ch, K, goal_pos, goal_quat, lambda2, dq, err, pos_targets, stream);
 }
 
+int launch_osc(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props, int n,
+               const IkChains &ch, int K, const float *goal_pos, const float *goal_quat, const float *q_rest,
+               const OscGains &gains, float *tau, float *err, float *efforts, hipStream_t stream) {
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(osc_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, props, n, ch, K, goal_pos,
+                 goal_quat, q_rest, gains, tau, err, efforts);
+    }) ? rc : jit_launch_osc(hash, root, dof, mass_scale, props, n, ch, K, goal_pos, goal_quat, q_rest, gains, tau,
+                             err, efforts, stream);
+}
+
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {

@@ -1224,6 +1224,260 @@ __global__ __launch_bounds__(64) void ik_dls_kernel(const float *root, const flo
     }
 }
 
+// Operational-space control (tgsim.h tg_osc), _compute_osc_torques of
+// tasks/franka_cube_stack.py:602-628 in one launch: the torque-level
+// counterpart of ik_dls_kernel, with the same chains, controlled point, pose
+// error and J columns, and the chain's own block H_c of the mass matrix.  One
+// wavefront per env, lane = 8 k + c = (chain, column):
+//   lanes        forward kinematics, then the composite inertias of
+//                mass_matrix_kernel (10 floats per link about the root origin,
+//                mass-scaled, summed into the ancestors)
+//   lane k       the controlled point and the pose error, as in the IK
+//   lane (k, c)  the J column as in the IK; F = I^c s of the column's joint and
+//                H_c[c][j] = s_j . F for every chain column j whose joint is an
+//                ancestor-or-self (the JacTables ancestor table instead of a
+//                walk up the tree: the loads are independent), written with
+//                H_c[j][c] from the one value, the armature on the diagonal;
+//                z = kd qd + a, a the null-space acceleration
+//   lane (k, r)  every lane of the chain factors the 8 x 8 tile H_c = L L^T in
+//                registers (columns past num_dofs are an identity block; the
+//                same work on all eight lanes costs no time), then lane r < R
+//                solves L w_r = (row r of J)^T and forms b_r = kp err_r - J_r z
+//   lanes        the packed lower triangle of W^T W + lambda^2 I per chain
+//   lane k       y = (W^T W + lambda^2 I)^-1 b by ik_chol_solve
+//   lane (k, c)  tau = column . y + (H_c a)_c
+//   lane d       efforts[e, d] = clamp(sum of tau over (k, c) with dofs[c] == d)
+// tau = J^T L (kp err - kd v) + H_c a - J^T L (J a) is evaluated as J^T L (kp
+// err - J (kd qd + a)) + H_c a, one solve.  Wave-level syncs only.
+template <class M>
+__global__ __launch_bounds__(64) void osc_kernel(const float *root, const float *dof, const float *mass_scale,
+                                                 const float *props, int n, IkChains ch, int K,
+                                                 const float *goal_pos, const float *goal_quat, const float *q_rest,
+                                                 OscGains gn, float *tau, float *err, float *efforts) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    static_assert(TG_IK_MAX_CHAINS * TG_IK_MAX_DOFS <= 64, "one lane per (chain, column)");
+    static_assert(TG_IK_MAX_DOFS == 8, "the H_c tile and its factorisation are 8 x 8");
+    using JT = JacTables<M>;
+    constexpr int MC = TG_IK_MAX_CHAINS, MD = TG_IK_MAX_DOFS;
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    K = K < 1 ? 1 : (K > MC ? MC : K);
+    __shared__ float T[M::NL][12], A[M::NL][3], IC[M::NL][10];
+    __shared__ float X[MC][3], E[MC][6], Jc[MC * MD][6], Hc[MC][MD][MD], Z[MC * MD], AN[MC * MD];
+    __shared__ float W[MC][6][MD], B[MC][6], G[MC][21], Y[MC][6], TAU[MC * MD];
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e, *q = dof + 2 * (size_t)e * M::ND;
+    const bool orient = goal_quat != nullptr;
+    const int NR = orient ? 6 : 3, NT = orient ? 21 : 6;
+    fk_root_relative<M>(r, q, lane, T, A);
+    // every link's inertia about the root origin, world axes (mass_matrix_kernel's)
+    for (int l = lane; l < M::NL; l += 64) {
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const float *li = M::link_inertia[l];
+        const float sc = mass_scale ? mass_scale[(size_t)e * M::NL + l] : 1.f;
+        const float m = sc * li[0];
+        const V3 c = v3(T[l][9], T[l][10], T[l][11]) + mul(R, v3(li[1], li[2], li[3]));
+        float I[6];
+        sym_rot(li + 4, transpose(R), I);   // R I R^T
+        const float c2 = dot(c, c);
+        IC[l][0] = m;
+        IC[l][1] = m * c.x; IC[l][2] = m * c.y; IC[l][3] = m * c.z;
+        IC[l][4] = sc * I[0] + m * (c2 - c.x * c.x);
+        IC[l][5] = sc * I[1] + m * (c2 - c.y * c.y);
+        IC[l][6] = sc * I[2] + m * (c2 - c.z * c.z);
+        IC[l][7] = sc * I[3] - m * c.x * c.y;
+        IC[l][8] = sc * I[4] - m * c.x * c.z;
+        IC[l][9] = sc * I[5] - m * c.y * c.z;
+    }
+    // the H_c tiles start as the identity: what the chains do not fill stays factorisable
+    for (int i = lane; i < MC * MD * MD; i += 64) (&Hc[0][0][0])[i] = (i / MD) % MD == i % MD ? 1.f : 0.f;
+    wsync();
+    if (lane < 10) {
+#pragma unroll
+        for (int k = M::NL - 1; k >= 1; --k) IC[M::link_parent[k]][lane] += IC[k][lane];
+    }
+    if (lane < K) {   // the controlled point and the pose error: ik_dls_kernel's
+        const int k = lane, l = ch.c[k].link;
+        M3 Rl;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Rl.a[i] = T[l][i];
+        const V3 x = v3(T[l][9], T[l][10], T[l][11]) + mul(Rl, v3(ch.c[k].offset[0], ch.c[k].offset[1], ch.c[k].offset[2]));
+        const float *gp = goal_pos + ((size_t)e * K + k) * 3;
+        const V3 el = (v3(gp[0], gp[1], gp[2]) - v3(r[0], r[1], r[2])) - x;
+        V3 eo = v3(0.f, 0.f, 0.f);
+        if (orient) {
+            const float *gq = goal_quat + ((size_t)e * K + k) * 4;
+            float gx = gq[0], gy = gq[1], gz = gq[2], gw = gq[3];
+            const float in = 1.0f / sqrtf(gx * gx + gy * gy + gz * gz + gw * gw);
+            gx *= in; gy *= in; gz *= in; gw *= in;
+            float lx, ly, lz, lw;
+            m3_to_quat(Rl, lx, ly, lz, lw);
+            // q_goal (x) conj(q_l)
+            const V3 gv = v3(gx, gy, gz), lv = v3(lx, ly, lz);
+            const float w = gw * lw + dot(gv, lv);
+            const V3 v = (lw * gv - gw * lv) - cross(gv, lv);
+            eo = w >= 0.f ? v : -v;
+        }
+        X[k][0] = x.x; X[k][1] = x.y; X[k][2] = x.z;
+        E[k][0] = el.x; E[k][1] = el.y; E[k][2] = el.z;
+        E[k][3] = eo.x; E[k][4] = eo.y; E[k][5] = eo.z;
+        if (err) {
+            float *o = err + ((size_t)e * K + k) * 6;
+            o[0] = el.x; o[1] = el.y; o[2] = el.z;
+            o[3] = eo.x; o[4] = eo.y; o[5] = eo.z;
+        }
+    }
+    wsync();
+    const int ck = lane / MD, cc = lane % MD;   // this lane's (chain, column)
+    const int nd = ck < K ? ch.c[ck].num_dofs : 0;
+    bool live = false;                          // a column on the link's path
+    {
+        V3 lin = v3(0.f, 0.f, 0.f), ang = v3(0.f, 0.f, 0.f);
+        float z = 0.f, an = 0.f;
+        if (cc < nd) {
+            const int l = ch.c[ck].link, d = ch.c[ck].dofs[cc];
+            const int j = JT::dof_link.v[d];
+            const V3 a = v3(A[j][0], A[j][1], A[j][2]), p = v3(T[j][9], T[j][10], T[j][11]);
+            const bool prismatic = M::link_jtype[j] == TG_JOINT_PRISMATIC;
+            if (JT::anc.v[l * JT::ND1 + d]) {
+                live = true;
+                if (prismatic) {
+                    lin = a;
+                } else {
+                    lin = cross(a, v3(X[ck][0], X[ck][1], X[ck][2]) - p);
+                    ang = a;
+                }
+            }
+            // F = I^c_j s_j, and its products with the motions of the chain's joints at or above j
+            V3 nn, ff;
+            comp_mul(IC[j], prismatic ? JointMotion{v3(0.f, 0.f, 0.f), a} : JointMotion{a, cross(p, a)}, nn, ff);
+            for (int c2 = 0; c2 < nd; ++c2) {
+                const int d2 = ch.c[ck].dofs[c2];
+                if (!JT::anc.v[j * JT::ND1 + d2]) continue;
+                const int j2 = JT::dof_link.v[d2];
+                const V3 a2 = v3(A[j2][0], A[j2][1], A[j2][2]);
+                float v;
+                if (M::link_jtype[j2] == TG_JOINT_PRISMATIC)
+                    v = dot(a2, ff);
+                else
+                    v = dot(a2, nn) + dot(cross(v3(T[j2][9], T[j2][10], T[j2][11]), a2), ff);
+                if (c2 == cc) v += props[((size_t)TG_PROP_ARMATURE * n + e) * M::ND + d];
+                Hc[ck][cc][c2] = v;
+                Hc[ck][c2][cc] = v;
+            }
+            if (q_rest) {
+                float x = q_rest[(size_t)e * M::ND + d] - q[2 * d];
+                if (!prismatic) x -= 6.283185307179586f * floorf((x + 3.141592653589793f) / 6.283185307179586f);
+                an = gn.kp_null * x - gn.kd_null * q[2 * d + 1];
+            }
+            z = gn.kd * q[2 * d + 1] + an;
+        }
+        Jc[lane][0] = lin.x; Jc[lane][1] = lin.y; Jc[lane][2] = lin.z;
+        Jc[lane][3] = ang.x; Jc[lane][4] = ang.y; Jc[lane][5] = ang.z;
+        Z[lane] = z;
+        AN[lane] = an;
+    }
+    wsync();
+    {
+        // H_c = L L^T, the diagonal kept inverted; every lane of the chain holds L
+        float L[MD][MD];
+#pragma unroll
+        for (int j = 0; j < MD; ++j) {
+            float d = Hc[ck][j][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+            const float inv = 1.0f / sqrtf(d);
+            L[j][j] = inv;
+#pragma unroll
+            for (int i = j + 1; i < MD; ++i) {
+                float s = Hc[ck][i][j];
+#pragma unroll
+                for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+                L[i][j] = s * inv;
+            }
+        }
+        if (ck < K && cc < NR) {
+            float w[MD], b = gn.kp * E[ck][cc];
+#pragma unroll
+            for (int j = 0; j < MD; ++j) {   // L w = (row cc of J)^T
+                const float jr = Jc[ck * MD + j][cc];
+                float s = jr;
+#pragma unroll
+                for (int k = 0; k < j; ++k) s -= L[j][k] * w[k];
+                w[j] = s * L[j][j];
+                W[ck][cc][j] = w[j];
+                b -= jr * Z[ck * MD + j];
+            }
+            B[ck][cc] = b;
+        }
+    }
+    wsync();
+    for (int i = lane; i < K * NT; i += 64) {
+        const int k = i / NT, t = i - k * NT;
+        const int rr = t >= 15 ? 5 : (t >= 10 ? 4 : (t >= 6 ? 3 : (t >= 3 ? 2 : (t >= 1 ? 1 : 0))));
+        const int ss = t - rr * (rr + 1) / 2;
+        float s = rr == ss ? gn.lambda2 : 0.f;
+#pragma unroll
+        for (int c = 0; c < MD; ++c) s += W[k][rr][c] * W[k][ss][c];
+        G[k][t] = s;
+    }
+    wsync();
+    if (lane < K) {
+        float g[21], b[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, y[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (orient) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) b[i] = B[lane][i];
+#pragma unroll
+            for (int i = 0; i < 21; ++i) g[i] = G[lane][i];
+            ik_chol_solve<6>(g, b, y);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) b[i] = B[lane][i];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) g[i] = G[lane][i];
+            ik_chol_solve<3>(g, b, y);
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) Y[lane][i] = y[i];
+    }
+    wsync();
+    if (ck < K) {
+        float u = 0.f;
+        if (live)
+            for (int i = 0; i < NR; ++i) u += Jc[lane][i] * Y[ck][i];
+        if (q_rest && cc < nd) {
+            float h = 0.f;
+            for (int c2 = 0; c2 < nd; ++c2) h += Hc[ck][cc][c2] * AN[ck * MD + c2];
+            u += h;
+        }
+        TAU[lane] = u;
+        if (tau) tau[((size_t)e * K + ck) * MD + cc] = u;
+    }
+    if (!efforts) return;
+    wsync();
+    for (int d = lane; d < M::ND; d += 64) {
+        float s = 0.f;
+        bool hit = false;
+        for (int k = 0; k < K; ++k)
+            for (int c = 0; c < ch.c[k].num_dofs; ++c)
+                if (ch.c[k].dofs[c] == d) {
+                    s += TAU[k * MD + c];
+                    hit = true;
+                }
+        if (hit) {
+            const float lim = props[((size_t)TG_PROP_EFFORT * n + e) * M::ND + d];
+            efforts[(size_t)e * M::ND + d] = fminf(fmaxf(s, -lim), lim);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- rigid-body forces
 // apply_rigid_body_force_tensors (reference call site
 // tasks/gogoro_realistic_turning_sim_paper.py:457): per-link forces [N*L,3] at

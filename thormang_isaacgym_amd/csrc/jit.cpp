@@ -34,7 +34,7 @@
 namespace tg {
 namespace {
 
-enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, NK };
+enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, NK };
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, false, tg::NoPost>",
@@ -44,6 +44,7 @@ const char *const KERNEL_EXPR[NK] = {
     "tg::jacobian_kernel<TgJitModel>",
     "tg::mass_matrix_kernel<TgJitModel>",
     "tg::ik_dls_kernel<TgJitModel>",
+    "tg::osc_kernel<TgJitModel>",
 };
 // the per-model launch figures the host needs, read back from the module
 // (tgjit_meta, same order)
@@ -152,7 +153,7 @@ int compile(const std::string &src, const std::string &incdir, JitCode &out, std
     return 0;
 }
 
-// cache file: "TGJIT3\n", one lowered name per line, then the code object
+// cache file: "TGJIT4\n", one lowered name per line, then the code object
 bool cache_load(const std::string &path, JitCode &out) {
     std::string s;
     if (!read_file(path, s)) return false;
@@ -165,7 +166,7 @@ bool cache_load(const std::string &path, JitCode &out) {
         return true;
     };
     std::string magic;
-    if (!line(magic) || magic != "TGJIT3") return false;
+    if (!line(magic) || magic != "TGJIT4") return false;
     for (int k = 0; k < NK; ++k)
         if (!line(out.names[k]) || out.names[k].empty()) return false;
     if (pos >= s.size()) return false;
@@ -178,7 +179,7 @@ void cache_store(const std::string &path, const JitCode &c) {
     {
         std::ofstream f(tmp, std::ios::binary);
         if (!f) return;
-        f << "TGJIT3\n";
+        f << "TGJIT4\n";
         for (int k = 0; k < NK; ++k) f << c.names[k] << "\n";
         f.write(c.code.data(), (std::streamsize)c.code.size());
         if (!f) return;
@@ -332,6 +333,19 @@ int jit_launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n,
     IkChains cc = ch;
     void *args[] = {&root, &dof, &n, &cc, &K, &goal_pos, &goal_quat, &lambda2, &dq, &err, &pos_targets};
     return launch(L->f[K_IK], (unsigned)n, 64, 0, stream, args);
+}
+
+int jit_launch_osc(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props,
+                   int n, const IkChains &ch, int K, const float *goal_pos, const float *goal_quat,
+                   const float *q_rest, const OscGains &gains, float *tau, float *err, float *efforts,
+                   hipStream_t stream) {
+    JitLoaded *L = find(hash);
+    if (!L) return TG_ERR_MODEL;
+    IkChains cc = ch;
+    OscGains gg = gains;
+    void *args[] = {&root, &dof, &mass_scale, &props, &n, &cc, &K, &goal_pos, &goal_quat, &q_rest, &gg, &tau, &err,
+                    &efforts};
+    return launch(L->f[K_OSC], (unsigned)n, 64, 0, stream, args);
 }
 
 }  // namespace tg

@@ -20,6 +20,10 @@ constexpr int TG_PM_MAX_DOF = 64;   // prologue lanes: one wavefront per env, la
 struct IkChains {
     tg_ik_chain c[TG_IK_MAX_CHAINS];
 };
+// the gains of a tg_osc call as osc_kernel takes them: tg_osc_gains with the damping squared
+struct OscGains {
+    float kp, kd, kp_null, kd_null, lambda2;
+};
 
 // optional Gogoro pre-physics prologue of the compose launch (tg_gogoro_step)
 struct GogoroPre {
@@ -195,6 +199,10 @@ int launch_mass_matrices(uint64_t hash, const float *root, const float *dof, con
 int launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
                   const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
                   float *pos_targets, hipStream_t stream);
+// operational-space control of K chains per env (osc_kernel; tgsim.h tg_osc)
+int launch_osc(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props, int n,
+               const IkChains &ch, int K, const float *goal_pos, const float *goal_quat, const float *q_rest,
+               const OscGains &gains, float *tau, float *err, float *efforts, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
@@ -227,6 +235,10 @@ int jit_launch_mass_matrices(uint64_t hash, const float *root, const float *dof,
 int jit_launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
                       const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
                       float *pos_targets, hipStream_t stream);
+int jit_launch_osc(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props,
+                   int n, const IkChains &ch, int K, const float *goal_pos, const float *goal_quat,
+                   const float *q_rest, const OscGains &gains, float *tau, float *err, float *efforts,
+                   hipStream_t stream);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

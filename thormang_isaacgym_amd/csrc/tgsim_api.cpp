@@ -727,6 +727,29 @@ int tg_mass_matrices(tg_sim *s, float *out) {
     return TG_OK;
 }
 
+// the per-chain checks tg_ik_dls and tg_osc share (num_chains already in 1..TG_IK_MAX_CHAINS); fn: the call's
+// name for the message
+static int check_chains(const tg_sim *s, const char *fn, const tg_ik_chain *chains, int32_t num_chains,
+                        tg::IkChains &ch) {
+    for (int k = 0; k < num_chains; ++k) {
+        const tg_ik_chain &c = chains[k];
+        if (c.link < 0 || c.link >= s->L)
+            return fail(TG_ERR_ARG, "%s: chain %d: link %d outside [0, %d)", fn, k, c.link, s->L);
+        if (c.num_dofs < 1 || c.num_dofs > TG_IK_MAX_DOFS)
+            return fail(TG_ERR_ARG, "%s: chain %d: num_dofs %d outside 1..%d", fn, k, c.num_dofs, TG_IK_MAX_DOFS);
+        for (int i = 0; i < c.num_dofs; ++i) {
+            if (c.dofs[i] < 0 || c.dofs[i] >= s->D)
+                return fail(TG_ERR_ARG, "%s: chain %d: DOF %d outside [0, %d)", fn, k, c.dofs[i], s->D);
+            for (int j = 0; j < i; ++j)
+                if (c.dofs[j] == c.dofs[i])
+                    return fail(TG_ERR_ARG, "%s: chain %d: DOF %d appears twice", fn, k, c.dofs[i]);
+        }
+        ch.c[k] = c;
+        for (int i = c.num_dofs; i < TG_IK_MAX_DOFS; ++i) ch.c[k].dofs[i] = 0;   // ignored entries: nothing stale reaches the kernel
+    }
+    return TG_OK;
+}
+
 int tg_ik_dls(tg_sim *s, const tg_ik_chain *chains, int32_t num_chains, const float *goal_pos,
               const float *goal_quat, float damping, float *dq, float *err, float *pos_targets) {
     if (int rc = check_sim(s)) return rc;
@@ -737,27 +760,39 @@ int tg_ik_dls(tg_sim *s, const tg_ik_chain *chains, int32_t num_chains, const fl
         return fail(TG_ERR_ARG, "tg_ik_dls: damping %g is not a finite number > 0", (double)damping);
     if (!dq && !err && !pos_targets) return fail(TG_ERR_ARG, "tg_ik_dls: dq, err and pos_targets are all null");
     tg::IkChains ch{};
-    for (int k = 0; k < num_chains; ++k) {
-        const tg_ik_chain &c = chains[k];
-        if (c.link < 0 || c.link >= s->L)
-            return fail(TG_ERR_ARG, "tg_ik_dls: chain %d: link %d outside [0, %d)", k, c.link, s->L);
-        if (c.num_dofs < 1 || c.num_dofs > TG_IK_MAX_DOFS)
-            return fail(TG_ERR_ARG, "tg_ik_dls: chain %d: num_dofs %d outside 1..%d", k, c.num_dofs, TG_IK_MAX_DOFS);
-        for (int i = 0; i < c.num_dofs; ++i) {
-            if (c.dofs[i] < 0 || c.dofs[i] >= s->D)
-                return fail(TG_ERR_ARG, "tg_ik_dls: chain %d: DOF %d outside [0, %d)", k, c.dofs[i], s->D);
-            for (int j = 0; j < i; ++j)
-                if (c.dofs[j] == c.dofs[i])
-                    return fail(TG_ERR_ARG, "tg_ik_dls: chain %d: DOF %d appears twice", k, c.dofs[i]);
-        }
-        ch.c[k] = c;
-        for (int i = c.num_dofs; i < TG_IK_MAX_DOFS; ++i) ch.c[k].dofs[i] = 0;   // ignored entries: nothing stale reaches the kernel
-    }
+    if (int rc = check_chains(s, "tg_ik_dls", chains, num_chains, ch)) return rc;
     DeviceGuard dg(s->device);
     win_touch(s);
     if (int rc = tg::launch_ik_dls(s->hash, s->root, s->dof, (int)s->N, ch, num_chains, goal_pos, goal_quat,
                                    damping * damping, dq, err, pos_targets, s->stream))
         return fail(rc, "tg_ik_dls: launch failed");
+    return TG_OK;
+}
+
+int tg_osc(tg_sim *s, const tg_ik_chain *chains, int32_t num_chains, const float *goal_pos, const float *goal_quat,
+           const float *q_rest, const tg_osc_gains *gains, float *tau, float *err, float *efforts) {
+    if (int rc = check_sim(s)) return rc;
+    if (!chains || !goal_pos || !gains)
+        return fail(TG_ERR_ARG, "tg_osc: null %s", !chains ? "chains" : (!goal_pos ? "goal_pos" : "gains"));
+    if (num_chains < 1 || num_chains > TG_IK_MAX_CHAINS)
+        return fail(TG_ERR_ARG, "tg_osc: num_chains %d outside 1..%d", num_chains, TG_IK_MAX_CHAINS);
+    const tg_osc_gains g = *gains;
+    if (!(g.damping > 0.f) || !std::isfinite(g.damping))
+        return fail(TG_ERR_ARG, "tg_osc: damping %g is not a finite number > 0", (double)g.damping);
+    const struct { const char *name; float v; } gs[] = {{"kp", g.kp}, {"kd", g.kd}, {"kp_null", g.kp_null},
+                                                       {"kd_null", g.kd_null}};
+    for (const auto &x : gs)
+        if (!(x.v >= 0.f) || !std::isfinite(x.v))
+            return fail(TG_ERR_ARG, "tg_osc: %s %g is not a finite number >= 0", x.name, (double)x.v);
+    if (!tau && !err && !efforts) return fail(TG_ERR_ARG, "tg_osc: tau, err and efforts are all null");
+    tg::IkChains ch{};
+    if (int rc = check_chains(s, "tg_osc", chains, num_chains, ch)) return rc;
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    const tg::OscGains kg{g.kp, g.kd, g.kp_null, g.kd_null, g.damping * g.damping};
+    if (int rc = tg::launch_osc(s->hash, s->root, s->dof, s->mass_scale, s->props, (int)s->N, ch, num_chains, goal_pos,
+                                goal_quat, q_rest, kg, tau, err, efforts, s->stream))
+        return fail(rc, "tg_osc: launch failed");
     return TG_OK;
 }
 

@@ -486,6 +486,64 @@ class Sim:
                               _ptr(targets)), "solve_ik")
         return (dq, err) if return_error else dq
 
+    def solve_osc(self, chains, goal_pos: torch.Tensor, goal_quat: torch.Tensor | None = None, kp: float = 150.0,
+                  kd: float | None = None, kp_null: float = 10.0, kd_null: float | None = None,
+                  q_rest: torch.Tensor | None = None, damping: float = 1e-2, efforts: torch.Tensor | None = None,
+                  return_error: bool = False):
+        """Operational-space control, _compute_osc_torques of
+        tasks/franka_cube_stack.py:602-628, in one kernel launch (tgsim.h
+        tg_osc): for each of the K ``chains`` (``ik_chain``) the joint torques
+        ``J^T Lambda (kp err - kd v)`` that pull the chain's controlled point
+        towards ``goal_pos`` [N, K, 3] and ``goal_quat`` [N, K, 4] (xyzw; None:
+        position only), ``Lambda = (J H_c^-1 J^T + damping^2 I)^-1`` with the
+        chain's own block ``H_c`` of the mass matrix, from the current state,
+        on the sim's stream.  ``kd`` and ``kd_null`` default to
+        ``2 sqrt(kp)`` and ``2 sqrt(kp_null)``, the reference's.  With
+        ``q_rest`` [N, D] the null-space term that draws the chain's joints to
+        ``q_rest`` without accelerating the point is added.  Returns ``tau``
+        [N, K, 8] (columns past a chain's DOFs are 0, not clamped), with
+        ``return_error`` also the pose error [N, K, 6]; both are owned by the
+        sim and overwritten by the next call with as many chains.  With
+        ``efforts`` [N, D] (e.g. ``dof_actuation``) the kernel also writes the
+        torques, summed over the chains that share a DOF and clamped to the
+        DOF's effort limit, into the chain DOFs' columns and leaves the others
+        alone."""
+        chains = list(chains)
+        K = len(chains)
+        if not 1 <= K <= abi.TG_IK_MAX_CHAINS:
+            raise ValueError(f"solve_osc takes 1..{abi.TG_IK_MAX_CHAINS} chains, got {K}")
+
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        N = self.num_envs
+        checked(goal_pos, (N, K, 3), "goal_pos")
+        if goal_quat is not None:
+            checked(goal_quat, (N, K, 4), "goal_quat")
+        if q_rest is not None:
+            checked(q_rest, (N, self.D), "q_rest")
+        if efforts is not None:
+            checked(efforts, (N, self.D), "efforts")
+        kd = 2.0 * float(kp) ** 0.5 if kd is None else kd
+        kd_null = 2.0 * float(kp_null) ** 0.5 if kd_null is None else kd_null
+        gains = abi.tg_osc_gains(float(kp), float(kd), float(kp_null), float(kd_null), float(damping))
+        out = getattr(self, "_osc_out", None)
+        if out is None:
+            out = self._osc_out = {}
+        if K not in out:
+            out[K] = (torch.zeros(N, K, abi.TG_IK_MAX_DOFS, dtype=torch.float32, device=self.device),
+                      torch.zeros(N, K, 6, dtype=torch.float32, device=self.device))
+        tau, err = out[K]
+        arr = (abi.tg_ik_chain * K)(*chains)
+        check(lib().tg_osc(self._h, arr, K, _ptr(goal_pos), _ptr(goal_quat), _ptr(q_rest), C.byref(gains), _ptr(tau),
+                           _ptr(err), _ptr(efforts)), "solve_osc")
+        return (tau, err) if return_error else tau
+
     @property
     def contact_link_indices(self) -> list:
         return contact_link_indices(self.model)

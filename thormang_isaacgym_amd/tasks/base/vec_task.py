@@ -281,6 +281,14 @@ class VecTask(Env):
         return self.sim.solve_ik(chains, goal_pos, goal_quat=goal_quat, damping=damping, targets=targets,
                                  return_error=return_error)
 
+    def solve_osc(self, chains, goal_pos, goal_quat=None, kp=150.0, kd=None, kp_null=10.0, kd_null=None, q_rest=None,
+                  damping=1e-2, efforts=None, return_error=False):
+        """Operational-space control in one kernel: the torques [N, K, 8] that pull each chain's point to
+        its goal, optionally summed and clamped into ``efforts`` [N, D] (Sim.solve_osc)."""
+        return self.sim.solve_osc(chains, goal_pos, goal_quat=goal_quat, kp=kp, kd=kd, kp_null=kp_null,
+                                  kd_null=kd_null, q_rest=q_rest, damping=damping, efforts=efforts,
+                                  return_error=return_error)
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)
