@@ -538,7 +538,10 @@ void tg_model_free(tg_model *model);
  * the step kernel reads, built from the lock windows and mass scales) to the
  * device buffer out; with recompose != 0 every env is first re-composed from
  * scratch.  Checks the Gogoro epilogue's in-place seat update against a full
- * compose. */
+ * compose.  The re-compose is the launch a simulate makes for dirty envs,
+ * shared-cache check included (compose_kernel, then uniform_check_kernel): it
+ * leaves the shared-cache flag describing the blocks it wrote, so the next
+ * simulate may skip its own compose whether or not the envs still agree. */
 int tg_composite(tg_sim *sim, float *out, int32_t recompose);
 
 /* Random-number instrumentation (no reference counterpart; the task kernels'
@@ -560,6 +563,20 @@ int tg_rng_fill(tg_sim *sim, int32_t kind, uint64_t seed, uint64_t counter, floa
  * identical envs, one with a fill before every step, and require bit-identical
  * results. */
 int tg_debug_fill_lds(tg_sim *sim, uint32_t pattern);
+
+/* Launch-statistics instrumentation (no reference counterpart; tests): the
+ * host counters of the launches tg_simulate and the task steps made or skipped
+ * since the sim was created -- out[0] full compose launches (every dirty env),
+ * out[1] list compose launches (the last fused epilogue's resets), out[2]
+ * simulates that skipped the compose launch, out[3] launches of the
+ * rigid-body force reduction on its own (a pending
+ * tg_apply_rigid_body_force_tensors while the compose is skipped or a list
+ * compose), out[4] pending force tensors reduced inside a full compose,
+ * out[5] fused task-step launches that were declined (the caller then took its
+ * general path).  Plain integers read on the host: no device work, and nothing
+ * about what is launched depends on them.  The call-sequence tests use them
+ * to show that the cached path under test was really taken. */
+int tg_debug_launch_stats(tg_sim *sim, int64_t out[6]);
 
 /* Benchmark instrumentation (no reference counterpart): with period > 0,
  * tg_simulate brackets every period-th articulation step kernel launch with HIP

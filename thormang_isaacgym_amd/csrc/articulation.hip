@@ -179,11 +179,17 @@ int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const f
     }) ? rc : jit_launch_rb_forces(hash, root, dof, comp, n, mass_scale, forces, torques, space, out, props, stream);
 }
 
+// the full compose of launch_compose (launch.h), shared-cache check included:
+// the flag a later step kernel reads describes the blocks this launch wrote
 int launch_compose_only(uint64_t hash, const StepArgs &a, hipStream_t stream) {
     int rc = 0;
     return with_model(hash, [&](auto m) {
         rc = run(compose_kernel<decltype(m)>, dim3((a.N + COMPOSE_WPB - 1) / COMPOSE_WPB), dim3(64 * COMPOSE_WPB),
                  stream, a);
+        if (rc == 0 && a.cuni) {
+            if (hipMemsetD32Async(a.cuni, 1, 1, stream) != hipSuccess) rc = TG_ERR_HIP;
+            else rc = run(uniform_check_kernel<decltype(m)>, dim3(a.N), dim3(64), stream, a);
+        }
     }) ? rc : TG_ERR_MODEL;
 }
 

@@ -121,6 +121,12 @@ struct tg_sim {
     bool rbf_prereduced = false;
     double timed_ms = 0.0;
     int64_t timed_launches = 0;
+    // launch statistics (tg_debug_launch_stats): plain host counters, kept by
+    // simulate_args -- [0] full compose launches, [1] list compose launches,
+    // [2] simulates that skipped the compose, [3] launch_rb_forces launches,
+    // [4] pending force tensors reduced inside a compose, [5] fused launches
+    // declined (rc 1)
+    int64_t stats[6] = {0, 0, 0, 0, 0, 0};
 
     template <class T> int alloc(T **p, size_t count) {
         void *q = nullptr;
@@ -528,7 +534,10 @@ static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, tg::StepPost post 
     // the net contact force and DOF force exports have no fused-epilogue
     // variant: the task steps take their general path (simulates, then the
     // post-physics launch)
-    if ((s->cf || s->df) && post.fused()) return 1;
+    if ((s->cf || s->df) && post.fused()) {
+        s->stats[5]++;
+        return 1;
+    }
     post.cf = s->cf;
     post.df = s->df;
     DeviceGuard dg(s->device);
@@ -566,6 +575,7 @@ static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, tg::StepPost post 
             if (int rc = tg::launch_rb_forces(s->hash, s->root, s->dof, s->comp, (int)s->N, s->mass_scale, s->rbf_f,
                                               s->rbf_t, s->rbf_space, s->force, s->props, s->stream))
                 return fail(rc, "rigid-body force launch failed");
+            s->stats[3]++;
             s->rbf_pending = false;   // s->force holds the reduced wrenches now
         }
     }
@@ -605,10 +615,17 @@ static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, tg::StepPost post 
             s->ev_free.push_back(s->win);
             s->win = {nullptr, nullptr};
         }
-        if (rc == 1) return 1;   // not launched (no such instantiation): caller falls back
+        if (rc == 1) {   // not launched (no such instantiation): caller falls back
+            s->stats[5]++;
+            return 1;
+        }
         return fail(rc, "step launch failed: %s", hipGetErrorString(hipGetLastError()));
     }
-    if (rb_in_compose) s->rbf_pending = false;
+    s->stats[a.skip_compose ? 2 : (a.compose_list ? 1 : 0)]++;
+    if (rb_in_compose) {
+        s->rbf_pending = false;
+        s->stats[4]++;
+    }
     if (s->timing > 0) s->timing_count++;
     if (ev.first) {
         s->ev_pending.push_back(ev);
@@ -847,6 +864,13 @@ int tg_composite(tg_sim *s, float *out, int32_t recompose) {
         s->dirty_possible = false;
     }
     HIPCHK(hipMemcpyAsync(out, s->comp, (size_t)s->N * s->KC * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    return TG_OK;
+}
+
+int tg_debug_launch_stats(tg_sim *s, int64_t out[6]) {
+    if (int rc = check_sim(s)) return rc;
+    if (!out) return fail(TG_ERR_ARG, "tg_debug_launch_stats: null output");
+    memcpy(out, s->stats, sizeof s->stats);
     return TG_OK;
 }
 
