@@ -63,6 +63,10 @@
  *                            one link's Jacobian block and the chain's block of
  *                            the mass matrix, clamped to the effort limits
  *                            (tasks/franka_cube_stack.py:602-628)
+ *   tg_inverse_dynamics      no reference counterpart (its arm is loaded with
+ *                            disable_gravity): the bias force h(q, u) -- gravity
+ *                            and Coriolis compensation -- and tau = H a + h in the
+ *                            coordinates of tg_jacobians / tg_mass_matrices
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -486,6 +490,61 @@ int tg_osc(tg_sim *sim, const tg_ik_chain *chains /* HOST */, int32_t num_chains
            float *tau,              /* [N, K, TG_IK_MAX_DOFS] device or NULL */
            float *err,              /* [N, K, 6] device or NULL */
            float *efforts);         /* [N, D] device or NULL */
+/* Inverse dynamics by one recursive Newton-Euler pass in one kernel: the
+ * generalised force tau = H a + h(q, u) of the equation of motion H u' + h =
+ * tau, in exactly the coordinates of tg_jacobians and tg_mass_matrices, and
+ * optionally its DOF entries clamped into an actuation tensor: gravity and
+ * Coriolis compensation for effort-mode drives (tg_osc has none), computed-
+ * torque control, feed-forward for the PD drives.  On demand, stream-ordered,
+ * computed from the current root and dof state, the sim's current gravity
+ * (tg_set_gravity included), the env's body mass scales and its
+ * TG_PROP_ARMATURE and TG_PROP_EFFORT rows; nothing of the sim is written.
+ * dofs is HOST memory, read during the call and not retained (it travels to
+ * the kernel as a bitmask in its arguments).
+ *
+ * Let u, J[e, l] (Jv, Jw), s_l, m_l, I_l, R_l and H be exactly those of
+ * tg_jacobians and tg_mass_matrices -- in particular u(0:6) = root_state[7:13],
+ * the base linear velocity being that of the root link's centre of mass -- and
+ * g the gravity vector.  Then
+ *   tau = H a + sum_l s_l [ Jv_l^T m_l (ab_l - [GRAVITY] g)
+ *                           + Jw_l^T (R_l I_l R_l^T alb_l + w_l x (R_l I_l R_l^T w_l)) ]
+ * where ab_l and alb_l are the velocity-product accelerations of link l: the
+ * time derivatives of Jv_l u and Jw_l u with u' held at 0, and w_l = Jw_l u.
+ * Without TG_ID_VELOCITY u is taken as 0, so ab, alb and w all vanish.  a is
+ * accel, 0 when accel is NULL; H a includes the armature on the diagonal.
+ *
+ * So tau[0:3] is the net force, tau[3:6] the net moment about the root link's
+ * centre of mass, tau[6 + d] DOF d's generalised force.  Locked DOFs are
+ * ordinary entries at their dof_state position and velocity, as in H.  All
+ * lever arms are formed relative to the root link's origin: the result does
+ * not depend on where the env sits on the grid.  Every element of tau is
+ * written.  With fix_base the call still writes the full layout: tau[:, 6:]
+ * with u(0:6) = 0 is the fixed-base result, rows 0..5 are then the reaction at
+ * the base.
+ *
+ * efforts: for every selected DOF d (dofs[0..num_dofs); every DOF with dofs
+ * NULL and num_dofs 0), with t = tau[6 + d]:
+ *   accumulate == 0:  efforts[e, d] = clamp(t, -TG_PROP_EFFORT[e, d], +TG_PROP_EFFORT[e, d])
+ *   accumulate != 0:  efforts[e, d] = clamp(efforts[e, d] + t, -TG_PROP_EFFORT[e, d], +TG_PROP_EFFORT[e, d])
+ * No other element of efforts is touched.  The intended use is tg_osc with
+ * efforts = the sim's live dof_actuation tensor, then this call with the same
+ * tensor, the chains' DOFs and accumulate = 1 on the same stream; note that
+ * this clamps twice: tg_osc clamps its own sum, and this call clamps that
+ * clamped value plus t.
+ *
+ * TG_ERR_ARG (message "tg_inverse_dynamics: ...") for a null sim, terms
+ * outside 0..3, terms == 0 with accel NULL, tau and efforts both NULL,
+ * num_dofs outside 0..D, dofs NULL with num_dofs > 0, a DOF outside [0, D), a
+ * DOF listed twice (and efforts on a model of more than 256 DOFs).  Every
+ * model, run-time (tg_model_jit) ones included. */
+#define TG_ID_GRAVITY  1   /* the -g term */
+#define TG_ID_VELOCITY 2   /* Coriolis / centrifugal terms */
+int tg_inverse_dynamics(tg_sim *sim, int32_t terms,   /* TG_ID_* mask, may be 0 only with accel */
+                        const float *accel,           /* [N, 6+D] device or NULL (= 0) */
+                        float *tau,                   /* [N, 6+D] device or NULL */
+                        float *efforts,               /* [N, D] device or NULL */
+                        const int32_t *dofs /* HOST */, int32_t num_dofs, /* NULL, 0: every DOF */
+                        int32_t accumulate);          /* 0: efforts = clamp(t); 1: efforts = clamp(efforts + t) */
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

@@ -60,6 +60,7 @@ class tg_state_view(C.Structure):
 
 
 TG_IK_MAX_CHAINS, TG_IK_MAX_DOFS = 8, 8
+TG_ID_GRAVITY, TG_ID_VELOCITY = 1, 2   # tg_inverse_dynamics terms
 
 
 class tg_ik_chain(C.Structure):

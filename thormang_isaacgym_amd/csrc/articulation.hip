@@ -169,6 +169,16 @@ int launch_osc(uint64_t hash, const float *root, const float *dof, const float *
                              err, efforts, stream);
 }
 
+int launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                            const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
+                            float *efforts, hipStream_t stream) {
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(inverse_dynamics_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, props, n, ia,
+                 accel, tau, efforts);
+    }) ? rc : jit_launch_inverse_dynamics(hash, root, dof, mass_scale, props, n, ia, accel, tau, efforts, stream);
+}
+
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {

@@ -1478,6 +1478,149 @@ __global__ __launch_bounds__(64) void osc_kernel(const float *root, const float 
     }
 }
 
+// Inverse dynamics (tgsim.h tg_inverse_dynamics): tau = H a + h(q, u) in the
+// coordinates of jacobian_kernel and mass_matrix_kernel, by one recursive
+// Newton-Euler pass in world axes about the root link's origin.  One wavefront
+// per env:
+//   lanes        forward kinematics (fk_root_relative)
+//   lane = link  outward, level by level: the link's angular velocity w, its
+//                angular acceleration al and the acceleration ao of its origin
+//                from the parent's -- the root starts from u(0:6), a(0:6) given
+//                at its COM and from -g, so gravity rides on every link's
+//                linear acceleration; a revolute joint adds a qd to w and
+//                a qdd + w_p x a qd to al, a prismatic one a qdd + 2 w_p x a qd
+//                to ao
+//   lane = link  f = s m (ao + al x rc + w x (w x rc)), rc the com from the
+//                origin; the moment s (R I R^T al + w x R I R^T w) + c x f about
+//                the root origin
+//   lanes 0..5   the subtree sums: links in descending index order, each added
+//                to its parent, lane t carrying float t (as the composites of
+//                mass_matrix_kernel)
+//   lane = DOF   the subtree wrench on the joint's axis -- the moment about the
+//                anchor for a revolute joint, the force for a prismatic one --
+//                plus armature qdd; tau and, for a selected DOF, efforts
+//   lanes 0..5   the base rows: the whole body's force, and its moment shifted
+//                to the root com
+// Without TG_ID_VELOCITY u is taken as 0, without accel a is.  Wave-level syncs
+// only, plain stores, no atomics.
+template <class M>
+__global__ __launch_bounds__(64) void inverse_dynamics_kernel(const float *root, const float *dof,
+                                                              const float *mass_scale, const float *props, int n,
+                                                              IdArgs ia, const float *accel, float *tau,
+                                                              float *efforts) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    using JT = JacTables<M>;
+    constexpr int C = 6 + M::ND;
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    __shared__ float T[M::NL][12], A[M::NL][3], V[M::NL][9], W[M::NL][6];
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e, *q = dof + 2 * (size_t)e * M::ND;
+    const float *ac = accel ? accel + (size_t)e * C : nullptr;
+    const bool vel = (ia.terms & TG_ID_VELOCITY) != 0;
+    const V3 zero = v3(0.f, 0.f, 0.f);
+    fk_root_relative<M>(r, q, lane, T, A);
+    // the root link's com relative to its origin, world axes
+    V3 c0;
+    {
+        M3 R0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R0.a[k] = T[0][k];
+        c0 = mul(R0, v3(M::link_inertia[0][1], M::link_inertia[0][2], M::link_inertia[0][3]));
+    }
+    constexpr int NP = (M::NL + 63) / 64;   // links per lane
+    for (int lev = 0; lev <= M::NDEPTH; ++lev) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int l = lane + 64 * p;
+            if (l >= M::NL || M::link_depth[l] != lev) continue;
+            const int pl = M::link_parent[l];
+            V3 w, al, ao;
+            if (pl < 0) {
+                w = vel ? v3(r[10], r[11], r[12]) : zero;
+                al = ac ? v3(ac[3], ac[4], ac[5]) : zero;
+                V3 acom = ac ? v3(ac[0], ac[1], ac[2]) : zero;
+                if (ia.terms & TG_ID_GRAVITY) acom = acom - v3(ia.g[0], ia.g[1], ia.g[2]);
+                ao = acom - cross(al, c0) - cross(w, cross(w, c0));
+            } else {
+                const V3 wp = v3(V[pl][0], V[pl][1], V[pl][2]), alp = v3(V[pl][3], V[pl][4], V[pl][5]);
+                const V3 rr = v3(T[l][9], T[l][10], T[l][11]) - v3(T[pl][9], T[pl][10], T[pl][11]);
+                const int d = M::link_dof[l];
+                const float qd = d >= 0 && vel ? q[2 * d + 1] : 0.f, qdd = d >= 0 && ac ? ac[6 + d] : 0.f;
+                const V3 a = v3(A[l][0], A[l][1], A[l][2]);
+                w = wp;
+                al = alp;
+                ao = v3(V[pl][6], V[pl][7], V[pl][8]) + cross(alp, rr) + cross(wp, cross(wp, rr));
+                if (M::link_jtype[l] == TG_JOINT_REVOLUTE) {
+                    w = w + qd * a;
+                    al = al + qdd * a + cross(wp, qd * a);
+                } else if (M::link_jtype[l] == TG_JOINT_PRISMATIC) {
+                    ao = ao + qdd * a + 2.f * cross(wp, qd * a);
+                }
+            }
+            V[l][0] = w.x; V[l][1] = w.y; V[l][2] = w.z;
+            V[l][3] = al.x; V[l][4] = al.y; V[l][5] = al.z;
+            V[l][6] = ao.x; V[l][7] = ao.y; V[l][8] = ao.z;
+        }
+        wsync();
+    }
+    // every link's force and its moment about the root origin, mass-scaled
+    for (int l = lane; l < M::NL; l += 64) {
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const float *li = M::link_inertia[l];
+        const float sc = mass_scale ? mass_scale[(size_t)e * M::NL + l] : 1.f;
+        const V3 rc = mul(R, v3(li[1], li[2], li[3])), c = v3(T[l][9], T[l][10], T[l][11]) + rc;
+        float I[6];
+        sym_rot(li + 4, transpose(R), I);   // R I R^T
+        const V3 w = v3(V[l][0], V[l][1], V[l][2]), al = v3(V[l][3], V[l][4], V[l][5]);
+        const V3 acom = v3(V[l][6], V[l][7], V[l][8]) + cross(al, rc) + cross(w, cross(w, rc));
+        const V3 f = (sc * li[0]) * acom;
+        const V3 nn = sc * (symmul(I, al) + cross(w, symmul(I, w))) + cross(c, f);
+        W[l][0] = f.x; W[l][1] = f.y; W[l][2] = f.z;
+        W[l][3] = nn.x; W[l][4] = nn.y; W[l][5] = nn.z;
+    }
+    wsync();
+    if (lane < 6) {
+#pragma unroll
+        for (int k = M::NL - 1; k >= 1; --k) W[M::link_parent[k]][lane] += W[k][lane];
+    }
+    wsync();
+    float *to = tau ? tau + (size_t)e * C : nullptr;
+    for (int d = lane; d < M::ND; d += 64) {
+        const int j = JT::dof_link.v[d];
+        const V3 a = v3(A[j][0], A[j][1], A[j][2]), f = v3(W[j][0], W[j][1], W[j][2]);
+        float t;
+        if (M::link_jtype[j] == TG_JOINT_PRISMATIC)
+            t = dot(a, f);
+        else
+            t = dot(a, v3(W[j][3], W[j][4], W[j][5]) - cross(v3(T[j][9], T[j][10], T[j][11]), f));
+        if (ac) t += props[((size_t)TG_PROP_ARMATURE * n + e) * M::ND + d] * ac[6 + d];
+        if (to) to[6 + d] = t;
+        if (efforts && d < 32 * TG_ID_MASK_WORDS && ((ia.mask[d >> 5] >> (d & 31)) & 1u)) {
+            const float lim = props[((size_t)TG_PROP_EFFORT * n + e) * M::ND + d];
+            float *o = efforts + (size_t)e * M::ND + d;
+            const float s = ia.accumulate ? *o + t : t;
+            *o = fminf(fmaxf(s, -lim), lim);
+        }
+    }
+    if (to && lane < 6) {
+        const V3 f = v3(W[0][0], W[0][1], W[0][2]);
+        const V3 nc = v3(W[0][3], W[0][4], W[0][5]) - cross(c0, f);   // the moment about the root com
+        const float o[6] = {f.x, f.y, f.z, nc.x, nc.y, nc.z};
+        float v = o[0];
+#pragma unroll
+        for (int k = 1; k < 6; ++k) v = lane == k ? o[k] : v;
+        to[lane] = v;
+    }
+}
+
 // ---------------------------------------------------------------- rigid-body forces
 // apply_rigid_body_force_tensors (reference call site
 // tasks/gogoro_realistic_turning_sim_paper.py:457): per-link forces [N*L,3] at

@@ -34,7 +34,7 @@
 namespace tg {
 namespace {
 
-enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, NK };
+enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, K_ID, NK };
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, false, tg::NoPost>",
@@ -45,6 +45,7 @@ const char *const KERNEL_EXPR[NK] = {
     "tg::mass_matrix_kernel<TgJitModel>",
     "tg::ik_dls_kernel<TgJitModel>",
     "tg::osc_kernel<TgJitModel>",
+    "tg::inverse_dynamics_kernel<TgJitModel>",
 };
 // the per-model launch figures the host needs, read back from the module
 // (tgjit_meta, same order)
@@ -153,7 +154,7 @@ int compile(const std::string &src, const std::string &incdir, JitCode &out, std
     return 0;
 }
 
-// cache file: "TGJIT4\n", one lowered name per line, then the code object
+// cache file: "TGJIT5\n", one lowered name per line, then the code object
 bool cache_load(const std::string &path, JitCode &out) {
     std::string s;
     if (!read_file(path, s)) return false;
@@ -166,7 +167,7 @@ bool cache_load(const std::string &path, JitCode &out) {
         return true;
     };
     std::string magic;
-    if (!line(magic) || magic != "TGJIT4") return false;
+    if (!line(magic) || magic != "TGJIT5") return false;
     for (int k = 0; k < NK; ++k)
         if (!line(out.names[k]) || out.names[k].empty()) return false;
     if (pos >= s.size()) return false;
@@ -179,7 +180,7 @@ void cache_store(const std::string &path, const JitCode &c) {
     {
         std::ofstream f(tmp, std::ios::binary);
         if (!f) return;
-        f << "TGJIT4\n";
+        f << "TGJIT5\n";
         for (int k = 0; k < NK; ++k) f << c.names[k] << "\n";
         f.write(c.code.data(), (std::streamsize)c.code.size());
         if (!f) return;
@@ -346,6 +347,16 @@ int jit_launch_osc(uint64_t hash, const float *root, const float *dof, const flo
     void *args[] = {&root, &dof, &mass_scale, &props, &n, &cc, &K, &goal_pos, &goal_quat, &q_rest, &gg, &tau, &err,
                     &efforts};
     return launch(L->f[K_OSC], (unsigned)n, 64, 0, stream, args);
+}
+
+int jit_launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                                const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
+                                float *efforts, hipStream_t stream) {
+    JitLoaded *L = find(hash);
+    if (!L) return TG_ERR_MODEL;
+    IdArgs aa = ia;
+    void *args[] = {&root, &dof, &mass_scale, &props, &n, &aa, &accel, &tau, &efforts};
+    return launch(L->f[K_ID], (unsigned)n, 64, 0, stream, args);
 }
 
 }  // namespace tg

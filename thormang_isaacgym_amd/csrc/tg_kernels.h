@@ -24,6 +24,14 @@ struct IkChains {
 struct OscGains {
     float kp, kd, kp_null, kd_null, lambda2;
 };
+// what a tg_inverse_dynamics call hands inverse_dynamics_kernel by value: the sim's gravity, the TG_ID_* mask,
+// and the DOFs whose efforts are written as a bitmask (bit d of word d / 32)
+constexpr int TG_ID_MASK_WORDS = 8;
+struct IdArgs {
+    float g[3];
+    int terms, accumulate;
+    uint32_t mask[TG_ID_MASK_WORDS];
+};
 
 // optional Gogoro pre-physics prologue of the compose launch (tg_gogoro_step)
 struct GogoroPre {
@@ -203,6 +211,11 @@ int launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, con
 int launch_osc(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props, int n,
                const IkChains &ch, int K, const float *goal_pos, const float *goal_quat, const float *q_rest,
                const OscGains &gains, float *tau, float *err, float *efforts, hipStream_t stream);
+// inverse dynamics tau = H a + h into tau [N, 6 + D] and / or efforts [N, D] (inverse_dynamics_kernel; tgsim.h
+// tg_inverse_dynamics)
+int launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                            const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
+                            float *efforts, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
@@ -239,6 +252,9 @@ int jit_launch_osc(uint64_t hash, const float *root, const float *dof, const flo
                    int n, const IkChains &ch, int K, const float *goal_pos, const float *goal_quat,
                    const float *q_rest, const OscGains &gains, float *tau, float *err, float *efforts,
                    hipStream_t stream);
+int jit_launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                                const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
+                                float *efforts, hipStream_t stream);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

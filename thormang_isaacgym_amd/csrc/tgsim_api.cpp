@@ -813,6 +813,40 @@ int tg_osc(tg_sim *s, const tg_ik_chain *chains, int32_t num_chains, const float
     return TG_OK;
 }
 
+int tg_inverse_dynamics(tg_sim *s, int32_t terms, const float *accel, float *tau, float *efforts,
+                        const int32_t *dofs, int32_t num_dofs, int32_t accumulate) {
+    if (!s) return fail(TG_ERR_ARG, "tg_inverse_dynamics: null tg_sim");
+    if (terms < 0 || terms > (TG_ID_GRAVITY | TG_ID_VELOCITY))
+        return fail(TG_ERR_ARG, "tg_inverse_dynamics: terms %d outside 0..%d", terms, TG_ID_GRAVITY | TG_ID_VELOCITY);
+    if (terms == 0 && !accel) return fail(TG_ERR_ARG, "tg_inverse_dynamics: no terms and no accel");
+    if (!tau && !efforts) return fail(TG_ERR_ARG, "tg_inverse_dynamics: tau and efforts are both null");
+    if (num_dofs < 0 || num_dofs > s->D)
+        return fail(TG_ERR_ARG, "tg_inverse_dynamics: num_dofs %d outside 0..%d", num_dofs, s->D);
+    if (num_dofs > 0 && !dofs) return fail(TG_ERR_ARG, "tg_inverse_dynamics: null dofs with num_dofs %d", num_dofs);
+    constexpr int MASK_BITS = 32 * tg::TG_ID_MASK_WORDS;
+    if (efforts && s->D > MASK_BITS)
+        return fail(TG_ERR_ARG, "tg_inverse_dynamics: efforts of a model with %d DOFs, more than %d", s->D, MASK_BITS);
+    tg::IdArgs ia{};
+    for (int i = 0; i < num_dofs; ++i) {
+        const int d = dofs[i];
+        if (d < 0 || d >= s->D) return fail(TG_ERR_ARG, "tg_inverse_dynamics: DOF %d outside [0, %d)", d, s->D);
+        for (int j = 0; j < i; ++j)
+            if (dofs[j] == d) return fail(TG_ERR_ARG, "tg_inverse_dynamics: DOF %d appears twice", d);
+        if (d < MASK_BITS) ia.mask[d >> 5] |= 1u << (d & 31);   // (beyond it only without efforts: nothing reads the mask)
+    }
+    if (num_dofs == 0)   // every DOF
+        for (int d = 0; d < s->D && d < MASK_BITS; ++d) ia.mask[d >> 5] |= 1u << (d & 31);
+    memcpy(ia.g, s->gravity, sizeof ia.g);
+    ia.terms = terms;
+    ia.accumulate = accumulate != 0;
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_inverse_dynamics(s->hash, s->root, s->dof, s->mass_scale, s->props, (int)s->N, ia, accel, tau,
+                                             efforts, s->stream))
+        return fail(rc, "tg_inverse_dynamics: launch failed");
+    return TG_OK;
+}
+
 int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
     if (int rc = check_sim(s)) return rc;
     if (!out) {

@@ -544,6 +544,55 @@ class Sim:
                            _ptr(err), _ptr(efforts)), "solve_osc")
         return (tau, err) if return_error else tau
 
+    def inverse_dynamics(self, accel: torch.Tensor | None = None, gravity: bool = True, velocity: bool = True,
+                         dofs=None, efforts: torch.Tensor | None = None, accumulate: bool = False,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+        """Inverse dynamics in one kernel launch (tgsim.h tg_inverse_dynamics):
+        ``tau = H a + h(q, u)`` [N, 6 + D] in the coordinates of the Jacobian
+        and mass-matrix tensors, from the current state, the sim's gravity, the
+        body mass scales and the armature, on the sim's stream.  ``gravity``
+        and ``velocity`` switch the two parts of the bias force ``h`` -- the
+        weight and the Coriolis / centrifugal terms; ``accel`` [N, 6 + D]
+        (None: 0) is the acceleration ``a``.  ``tau[:, :3]`` is the net force,
+        ``tau[:, 3:6]`` the net moment about the root link's centre of mass,
+        ``tau[:, 6 + d]`` DOF d's generalised force.  Returns ``out`` if given,
+        else a tensor owned by the sim that the next call overwrites.  With
+        ``efforts`` [N, D] (e.g. ``dof_actuation``) the kernel also writes DOF
+        d's entry, clamped to the DOF's effort limit, for every DOF in ``dofs``
+        (names or indices; None: all) and leaves the others alone; with
+        ``accumulate`` it adds to what ``efforts`` holds before it clamps --
+        after ``solve_osc(..., efforts=sim.dof_actuation)`` this is gravity and
+        Coriolis compensation of the controlled chains (clamped twice)."""
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        N, C_ = self.num_envs, 6 + self.D
+        if accel is not None:
+            checked(accel, (N, C_), "accel")
+        if efforts is not None:
+            checked(efforts, (N, self.D), "efforts")
+        if out is not None:
+            checked(out, (N, C_), "out")
+        else:
+            out = getattr(self, "_id_out", None)
+            if out is None:
+                out = self._id_out = torch.zeros(N, C_, dtype=torch.float32, device=self.device)
+        terms = (abi.TG_ID_GRAVITY if gravity else 0) | (abi.TG_ID_VELOCITY if velocity else 0)
+        if terms == 0 and accel is None:
+            raise ValueError("inverse_dynamics without gravity, velocity and accel has nothing to compute")
+        idx = [] if dofs is None else [self._name_index("dof", x) for x in dofs]
+        if dofs is not None and not idx:
+            raise ValueError("dofs is empty; pass None for every DOF")
+        arr = (C.c_int32 * len(idx))(*idx) if idx else None
+        check(lib().tg_inverse_dynamics(self._h, terms, _ptr(accel), _ptr(out), _ptr(efforts), arr, len(idx),
+                                        1 if accumulate else 0), "inverse_dynamics")
+        return out
+
     @property
     def contact_link_indices(self) -> list:
         return contact_link_indices(self.model)

@@ -289,6 +289,13 @@ class VecTask(Env):
                                   kd_null=kd_null, q_rest=q_rest, damping=damping, efforts=efforts,
                                   return_error=return_error)
 
+    def inverse_dynamics(self, accel=None, gravity=True, velocity=True, dofs=None, efforts=None, accumulate=False,
+                         out=None):
+        """Inverse dynamics in one kernel: ``tau = H a + h`` [N, 6 + D], gravity and Coriolis terms switchable,
+        optionally clamped into (or added to) ``efforts`` [N, D] for the chosen DOFs (Sim.inverse_dynamics)."""
+        return self.sim.inverse_dynamics(accel=accel, gravity=gravity, velocity=velocity, dofs=dofs, efforts=efforts,
+                                         accumulate=accumulate, out=out)
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)
