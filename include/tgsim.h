@@ -67,6 +67,11 @@
  *                            disable_gravity): the bias force h(q, u) -- gravity
  *                            and Coriolis compensation -- and tau = H a + h in the
  *                            coordinates of tg_jacobians / tg_mass_matrices
+ *   tg_centroidal            no reference counterpart: the whole-body centre of
+ *                            mass and its velocity, the angular momentum about it,
+ *                            the centroidal inertia, the centroidal momentum matrix
+ *                            A_G with h_G = A_G u and the momentum-rate bias A_G' u,
+ *                            in the coordinates of tg_jacobians / tg_mass_matrices
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -545,6 +550,64 @@ int tg_inverse_dynamics(tg_sim *sim, int32_t terms,   /* TG_ID_* mask, may be 0 
                         float *efforts,               /* [N, D] device or NULL */
                         const int32_t *dofs /* HOST */, int32_t num_dofs, /* NULL, 0: every DOF */
                         int32_t accumulate);          /* 0: efforts = clamp(t); 1: efforts = clamp(efforts + t) */
+/* Centroidal quantities of the floating-base robot in one kernel: the whole-
+ * body centre of mass (CoM) and its velocity, the angular momentum about the
+ * CoM, the total mass and the centroidal inertia (state), the centroidal
+ * momentum matrix A with h_G = A u (matrix) and the momentum-rate bias A' u
+ * (bias): what CoM height and velocity rewards, angular-momentum
+ * regularisation, capture-point termination, CoM-Jacobian balance IK and
+ * momentum-based whole-body control are built from.  On demand, stream-ordered,
+ * computed from the current root and dof state and the env's body mass scales
+ * (tg_set_body_mass_scale_indexed); nothing of the sim is written and nothing
+ * is kept on the host between calls.  Each output is optional: a NULL output
+ * is not touched and its part of the work is skipped; every element of every
+ * non-NULL output is written.
+ *
+ * Let u, J[e, l] = (Jv_l; Jw_l), c_l, R_l, I_l and s_l be exactly those of
+ * tg_jacobians and tg_mass_matrices, m'_l = s_l m_l and I'_l = s_l R_l I_l
+ * R_l^T.  Then
+ *   M = sum_l m'_l,   c = sum_l m'_l c_l / M,
+ *   A = sum_l [ m'_l Jv_l ; I'_l Jw_l + (c_l - c) x m'_l Jv_l ]     (6 x (6 + D))
+ * rows 0..2 of A give the linear momentum, rows 3..5 the angular momentum
+ * about c, world axes; A[0:3] / M is the CoM Jacobian.
+ *
+ * state[e], TG_CENTROIDAL_STATE = 16 floats:
+ *   [0:3]   c, in the world frame of tg_rigid_body_states
+ *   [3:6]   c', the CoM velocity; the linear momentum is M c'
+ *   [6:9]   k, the angular momentum about c
+ *   [9]     M
+ *   [10:16] I_G = sum_l (I'_l + m'_l (|d|^2 1 - d d^T)), d = c_l - c, in the
+ *           order xx yy zz xy xz yz of link_inertia
+ * so that A u = (M c', k) by definition.
+ *
+ * matrix[e] = A, row-major, in the column layout of tg_jacobians: base columns
+ * 0..5, DOF d at column 6 + d.  Armature does not enter.  A locked DOF is an
+ * ordinary column at its dof_state position, and its dof_state velocity enters
+ * the state (the rule of tg_jacobians).  A[0:3, 0:3] = M 1 with exact 0.0 off
+ * the diagonal and A[3:6, 0:3] = 0.0 (it vanishes identically, c being the
+ * CoM) are written exactly; mathematically A[3:6, 3:6] = I_G and A[0:3, 3:6] =
+ * -M [c - c_root]x, c_root the root link's centre of mass.  With fix_base the
+ * call still writes the full layout: matrix[:, :, 6:] is the fixed-base view.
+ *
+ * bias[e] = A' u, the momentum rate at u' = 0 without gravity, so that h_G' =
+ * A u' + bias: the net force and moment of the links' velocity-product
+ * inertial forces, the moment taken about c.  It equals the base rows of
+ * tg_inverse_dynamics(TG_ID_VELOCITY) with the moment moved from the root
+ * link's centre of mass to c.
+ *
+ * All lever arms are formed relative to the root link's origin; c is that
+ * relative CoM plus the root position, added last: every output other than
+ * state[0:3] is bit-identical wherever the env sits on the grid.  The outputs
+ * a call shares with a call that asks for fewer or more of them are
+ * bit-identical too.
+ *
+ * TG_ERR_ARG (message "tg_centroidal: ...") for a null sim or state, matrix
+ * and bias all NULL.  Every model, run-time (tg_model_jit) ones included. */
+#define TG_CENTROIDAL_STATE 16
+int tg_centroidal(tg_sim *sim,
+                  float *state,    /* [N, TG_CENTROIDAL_STATE] device or NULL */
+                  float *matrix,   /* [N, 6, 6+D] device or NULL */
+                  float *bias);    /* [N, 6] device or NULL */
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

@@ -61,6 +61,7 @@ class tg_state_view(C.Structure):
 
 TG_IK_MAX_CHAINS, TG_IK_MAX_DOFS = 8, 8
 TG_ID_GRAVITY, TG_ID_VELOCITY = 1, 2   # tg_inverse_dynamics terms
+TG_CENTROIDAL_STATE = 16                # floats per env of tg_centroidal's state
 
 
 class tg_ik_chain(C.Structure):

@@ -179,6 +179,15 @@ int launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, 
     }) ? rc : jit_launch_inverse_dynamics(hash, root, dof, mass_scale, props, n, ia, accel, tau, efforts, stream);
 }
 
+int launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n, float *state,
+                      float *matrix, float *bias, hipStream_t stream) {
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(centroidal_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, n, state, matrix,
+                 bias);
+    }) ? rc : jit_launch_centroidal(hash, root, dof, mass_scale, n, state, matrix, bias, stream);
+}
+
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {

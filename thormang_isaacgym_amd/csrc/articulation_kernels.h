@@ -1621,6 +1621,252 @@ __global__ __launch_bounds__(64) void inverse_dynamics_kernel(const float *root,
     }
 }
 
+// Centroidal quantities (tgsim.h tg_centroidal): the whole-body centre of mass
+// c, its velocity, the angular momentum k about it, the total mass M and the
+// centroidal inertia I_G into state [N, 16]; the centroidal momentum matrix A
+// [N, 6, 6 + D], A u = (M c', k), in the columns of jacobian_kernel; the
+// momentum-rate bias A' u [N, 6].  World axes, every lever arm relative to the
+// root link's origin.  One wavefront per env; which outputs are null is uniform
+// over the launch, so each part is skipped by a branch on its pointer:
+//   lane = link  the link's table rows, mass scale and joint rate into
+//                registers, ahead of the chain of passes
+//   lanes        forward kinematics (fk_root_relative)
+//   lane = link  the com from the origin, R I R^T (kept in registers), m' = s m
+//                and m' c_l
+//   lane = link  [state, bias] outward, level by level: the link's angular
+//                velocity w and the velocity vo of its origin from the parent's
+//                (the root from u(0:6), given at its com); [bias] also al and ao
+//                as inverse_dynamics_kernel forms them with a = 0 and no gravity
+//   every lane   sums m', m' c_l over the links in link order, so that each
+//                lane holds M and c
+//   lane = link  the link's 10-float mass moments about c (m', m' d, s R I R^T +
+//                m' (|d|^2 1 - d d^T), d = c_l - c); [state, bias] its momentum
+//                m' vc and angular momentum about c; [bias] its velocity-product
+//                inertial force and that force's moment about c
+//   lanes 4..21  [state, bias] lane t sums float t over the links in link order:
+//                I_G, M c', k, and the bias
+//   lanes 0..9   [matrix] the subtree composites about c, in place: links in
+//                descending index order, each added to its parent (as
+//                mass_matrix_kernel)
+//   lane = col   [matrix] the column's motion -- the joint's unit rate, or the
+//                base's, as the velocity of the body point at c -- times the
+//                subtree composite: its momentum and its angular momentum about c
+//                with no shift; A[0:6, 0:3] is written as (M 1, 0) exactly
+// The state is summed the same way whether the matrix is asked for or not, so
+// every call form gives the same bits.  Wave-level syncs only, plain stores, no
+// atomics.
+template <class M>
+__global__ __launch_bounds__(64) void centroidal_kernel(const float *root, const float *dof, const float *mass_scale,
+                                                        int n, float *state, float *matrix, float *bias) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    using JT = JacTables<M>;
+    constexpr int C = 6 + M::ND;
+    constexpr int SW = 23;   // floats per link of S, odd: lane = link writes fall on distinct banks
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    // V: w, vo, al, ao.  S: m', m' d, the inertia about c (the composite of comp_mul), the momentum, the angular
+    // momentum about c, the bias force and moment
+    __shared__ float T[M::NL][12], A[M::NL][3], V[M::NL][12], S[M::NL][SW];
+    __shared__ __align__(16) float H4[M::NL][4];   // m', m' c_l
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e, *q = dof + 2 * (size_t)e * M::ND;
+    const bool kin = state || bias;
+    // each lane's links first: the table and global reads stay out of the chain of passes below
+    constexpr int NP = (M::NL + 63) / 64;   // links per lane
+    int dep[NP], par[NP], jt[NP];
+    float sc[NP], qd[NP], li[NP][10];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int l = lane + 64 * p;
+        dep[p] = par[p] = -1;
+        jt[p] = 0;
+        sc[p] = qd[p] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 10; ++k) li[p][k] = 0.f;
+        if (l >= M::NL) continue;
+        dep[p] = M::link_depth[l];
+        par[p] = M::link_parent[l];
+        jt[p] = M::link_jtype[l];
+        const int d = M::link_dof[l];
+        qd[p] = d >= 0 && kin ? q[2 * d + 1] : 0.f;
+        sc[p] = mass_scale ? mass_scale[(size_t)e * M::NL + l] : 1.f;
+#pragma unroll
+        for (int k = 0; k < 10; ++k) li[p][k] = M::link_inertia[l][k];
+    }
+    fk_root_relative<M>(r, q, lane, T, A);
+    // the root link's com relative to its origin, world axes
+    V3 c0;
+    {
+        M3 R0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R0.a[k] = T[0][k];
+        c0 = mul(R0, v3(M::link_inertia[0][1], M::link_inertia[0][2], M::link_inertia[0][3]));
+    }
+    // per link: the com from the origin rc, R I R^T, and m', m' c_l for the sums below
+    V3 rc[NP], cl[NP];
+    float I[NP][6];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int l = lane + 64 * p;
+        rc[p] = cl[p] = v3(0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) I[p][k] = 0.f;
+        if (l >= M::NL) continue;
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        rc[p] = mul(R, v3(li[p][1], li[p][2], li[p][3]));
+        cl[p] = v3(T[l][9], T[l][10], T[l][11]) + rc[p];
+        sym_rot(li[p] + 4, transpose(R), I[p]);   // R I R^T
+        const float m = sc[p] * li[p][0];
+        *reinterpret_cast<float4 *>(H4[l]) = make_float4(m, m * cl[p].x, m * cl[p].y, m * cl[p].z);
+    }
+    if (kin) {
+        for (int lev = 0; lev <= M::NDEPTH; ++lev) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                if (dep[p] != lev) continue;
+                const int l = lane + 64 * p, pl = par[p];
+                V3 w, vo, al = v3(0.f, 0.f, 0.f), ao = al;
+                if (pl < 0) {
+                    w = v3(r[10], r[11], r[12]);
+                    vo = v3(r[7], r[8], r[9]) - cross(w, c0);
+                    if (bias) ao = -cross(w, cross(w, c0));
+                } else {
+                    const V3 wp = v3(V[pl][0], V[pl][1], V[pl][2]);
+                    const V3 rr = v3(T[l][9], T[l][10], T[l][11]) - v3(T[pl][9], T[pl][10], T[pl][11]);
+                    const V3 aq = qd[p] * v3(A[l][0], A[l][1], A[l][2]);
+                    w = wp;
+                    vo = v3(V[pl][3], V[pl][4], V[pl][5]) + cross(wp, rr);
+                    if (bias) {
+                        al = v3(V[pl][6], V[pl][7], V[pl][8]);
+                        ao = v3(V[pl][9], V[pl][10], V[pl][11]) + cross(al, rr) + cross(wp, cross(wp, rr));
+                    }
+                    if (jt[p] == TG_JOINT_REVOLUTE) {
+                        w = w + aq;
+                        if (bias) al = al + cross(wp, aq);
+                    } else if (jt[p] == TG_JOINT_PRISMATIC) {
+                        vo = vo + aq;
+                        if (bias) ao = ao + 2.f * cross(wp, aq);
+                    }
+                }
+                V[l][0] = w.x; V[l][1] = w.y; V[l][2] = w.z;
+                V[l][3] = vo.x; V[l][4] = vo.y; V[l][5] = vo.z;
+                if (bias) {
+                    V[l][6] = al.x; V[l][7] = al.y; V[l][8] = al.z;
+                    V[l][9] = ao.x; V[l][10] = ao.y; V[l][11] = ao.z;
+                }
+            }
+            wsync();
+        }
+    } else {
+        wsync();
+    }
+    // the total mass and the com relative to the root origin, in every lane
+    float Mt = 0.f;
+    V3 c = v3(0.f, 0.f, 0.f);
+    for (int l = 0; l < M::NL; ++l) {
+        const float4 h = *reinterpret_cast<const float4 *>(H4[l]);
+        Mt += h.x;
+        c = c + v3(h.y, h.z, h.w);
+    }
+    c = v3(c.x / Mt, c.y / Mt, c.z / Mt);
+    // every link's moments about c
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int l = lane + 64 * p;
+        if (l >= M::NL) continue;
+        const float m = sc[p] * li[p][0], s1 = sc[p];
+        const V3 d = cl[p] - c;
+        const float *Ip = I[p];
+        const float d2 = dot(d, d);
+        float *o = S[l];
+        o[0] = m;
+        o[1] = m * d.x; o[2] = m * d.y; o[3] = m * d.z;
+        o[4] = s1 * Ip[0] + m * (d2 - d.x * d.x);
+        o[5] = s1 * Ip[1] + m * (d2 - d.y * d.y);
+        o[6] = s1 * Ip[2] + m * (d2 - d.z * d.z);
+        o[7] = s1 * Ip[3] - m * d.x * d.y;
+        o[8] = s1 * Ip[4] - m * d.x * d.z;
+        o[9] = s1 * Ip[5] - m * d.y * d.z;
+        if (kin) {
+            const V3 w = v3(V[l][0], V[l][1], V[l][2]);
+            const V3 pm = m * (v3(V[l][3], V[l][4], V[l][5]) + cross(w, rc[p]));
+            const V3 kl = s1 * symmul(Ip, w) + cross(d, pm);
+            o[10] = pm.x; o[11] = pm.y; o[12] = pm.z;
+            o[13] = kl.x; o[14] = kl.y; o[15] = kl.z;
+            if (bias) {
+                const V3 al = v3(V[l][6], V[l][7], V[l][8]);
+                const V3 f = m * (v3(V[l][9], V[l][10], V[l][11]) + cross(al, rc[p]) + cross(w, cross(w, rc[p])));
+                const V3 nn = s1 * (symmul(Ip, al) + cross(w, symmul(Ip, w))) + cross(d, f);
+                o[16] = f.x; o[17] = f.y; o[18] = f.z;
+                o[19] = nn.x; o[20] = nn.y; o[21] = nn.z;
+            }
+        }
+    }
+    wsync();
+    if (lane >= 4 && lane < 22 && (lane < 16 ? state != nullptr : bias != nullptr)) {
+        float acc = 0.f;
+        for (int l = 0; l < M::NL; ++l) acc += S[l][lane];
+        if (lane < 10)
+            state[(size_t)e * TG_CENTROIDAL_STATE + 6 + lane] = acc;            // I_G
+        else if (lane < 13)
+            state[(size_t)e * TG_CENTROIDAL_STATE + lane - 7] = acc / Mt;       // the com velocity
+        else if (lane < 16)
+            state[(size_t)e * TG_CENTROIDAL_STATE + lane - 7] = acc;            // k
+        else
+            bias[(size_t)e * 6 + lane - 16] = acc;
+    }
+    if (state && lane < 4) {
+        // the root position is added last: the relative com does not depend on where the env sits
+        float v = Mt;
+        v = lane == 0 ? c.x + r[0] : v;
+        v = lane == 1 ? c.y + r[1] : v;
+        v = lane == 2 ? c.z + r[2] : v;
+        state[(size_t)e * TG_CENTROIDAL_STATE + (lane < 3 ? lane : 9)] = v;
+    }
+    if (!matrix) return;
+    if (lane < 10) {
+#pragma unroll
+        for (int k = M::NL - 1; k >= 1; --k) S[M::link_parent[k]][lane] += S[k][lane];
+    }
+    wsync();
+    float *o = matrix + (size_t)e * 6 * C;
+    for (int col = lane; col < C; col += 64) {
+        JointMotion s;   // (here v is the velocity of the body point at c)
+        const float *ic = S[0];
+        const V3 zero = v3(0.f, 0.f, 0.f);
+        const int k3 = col % 3;
+        const V3 ek = v3(k3 == 0 ? 1.f : 0.f, k3 == 1 ? 1.f : 0.f, k3 == 2 ? 1.f : 0.f);
+        if (col < 3) {
+            s = JointMotion{zero, ek};
+        } else if (col < 6) {
+            s = JointMotion{ek, cross(ek, c - c0)};   // rotation about the root com
+        } else {
+            const int j = JT::dof_link.v[col - 6];
+            const V3 a = v3(A[j][0], A[j][1], A[j][2]);
+            if (M::link_jtype[j] == TG_JOINT_PRISMATIC)
+                s = JointMotion{zero, a};
+            else
+                s = JointMotion{a, cross(a, c - v3(T[j][9], T[j][10], T[j][11]))};
+            ic = S[j];
+        }
+        V3 nn, ff;
+        comp_mul(ic, s, nn, ff);
+        if (col < 3) {   // exactly (M 1, 0): the first moment about the com vanishes identically
+            ff = Mt * ek;
+            nn = zero;
+        }
+        o[col] = ff.x; o[C + col] = ff.y; o[2 * C + col] = ff.z;
+        o[3 * C + col] = nn.x; o[4 * C + col] = nn.y; o[5 * C + col] = nn.z;
+    }
+}
+
 // ---------------------------------------------------------------- rigid-body forces
 // apply_rigid_body_force_tensors (reference call site
 // tasks/gogoro_realistic_turning_sim_paper.py:457): per-link forces [N*L,3] at

@@ -216,6 +216,10 @@ int launch_osc(uint64_t hash, const float *root, const float *dof, const float *
 int launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                             const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
                             float *efforts, hipStream_t stream);
+// centroidal state [N, 16], momentum matrix [N, 6, 6 + D] and momentum-rate bias [N, 6], each optional
+// (centroidal_kernel; tgsim.h tg_centroidal)
+int launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n, float *state,
+                      float *matrix, float *bias, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
@@ -255,6 +259,8 @@ int jit_launch_osc(uint64_t hash, const float *root, const float *dof, const flo
 int jit_launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                                 const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
                                 float *efforts, hipStream_t stream);
+int jit_launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n,
+                          float *state, float *matrix, float *bias, hipStream_t stream);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

@@ -847,6 +847,17 @@ int tg_inverse_dynamics(tg_sim *s, int32_t terms, const float *accel, float *tau
     return TG_OK;
 }
 
+int tg_centroidal(tg_sim *s, float *state, float *matrix, float *bias) {
+    if (!s) return fail(TG_ERR_ARG, "tg_centroidal: null tg_sim");
+    if (!state && !matrix && !bias) return fail(TG_ERR_ARG, "tg_centroidal: state, matrix and bias are all null");
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_centroidal(s->hash, s->root, s->dof, s->mass_scale, (int)s->N, state, matrix, bias,
+                                       s->stream))
+        return fail(rc, "tg_centroidal: launch failed");
+    return TG_OK;
+}
+
 int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
     if (int rc = check_sim(s)) return rc;
     if (!out) {

@@ -18,6 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import json
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -134,6 +135,9 @@ def contact_link_indices(model) -> list:
 
 def _ptr(t: torch.Tensor | None):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+Centroidal = namedtuple("Centroidal", ["state", "matrix", "bias"])   # what Sim.centroidal returns
 
 
 class Sim:
@@ -592,6 +596,50 @@ class Sim:
         check(lib().tg_inverse_dynamics(self._h, terms, _ptr(accel), _ptr(out), _ptr(efforts), arr, len(idx),
                                         1 if accumulate else 0), "inverse_dynamics")
         return out
+
+    def centroidal(self, matrix: bool = False, bias: bool = False, out: torch.Tensor | None = None,
+                   out_matrix: torch.Tensor | None = None, out_bias: torch.Tensor | None = None) -> "Centroidal":
+        """Centroidal quantities in one kernel launch (tgsim.h tg_centroidal),
+        from the current state and the body mass scales, on the sim's stream.
+        Returns ``Centroidal(state, matrix, bias)``.  ``state`` [N, 16]: the
+        whole-body centre of mass ``[0:3]`` (world), its velocity ``[3:6]``,
+        the angular momentum about it ``[6:9]``, the total mass ``[9]`` and the
+        centroidal inertia ``[10:16]`` (xx yy zz xy xz yz).  With ``matrix``
+        the centroidal momentum matrix ``A`` [N, 6, 6 + D] in the columns of
+        the Jacobian tensor, ``A u = (M c', k)``, ``A[:, :3] / M`` the CoM
+        Jacobian; with ``bias`` the momentum rate ``A' u`` [N, 6] at ``u' = 0``
+        without gravity.  A part that was not requested is None and costs
+        nothing.  ``out``, ``out_matrix`` and ``out_bias`` are checked and, for
+        a requested part, written and returned as given; an ``out_matrix`` or
+        ``out_bias`` passed without ``matrix`` / ``bias`` is left untouched.
+        Without them the tensors are owned by the sim and overwritten by the
+        next call."""
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        def own(key, shape):
+            buf = getattr(self, "_centroidal_out", None)
+            if buf is None:
+                buf = self._centroidal_out = {}
+            if key not in buf:
+                buf[key] = torch.zeros(*shape, dtype=torch.float32, device=self.device)
+            return buf[key]
+
+        N = self.num_envs
+        shapes = {"out": (N, abi.TG_CENTROIDAL_STATE), "out_matrix": (N, 6, 6 + self.D), "out_bias": (N, 6)}
+        given = {"out": out, "out_matrix": out_matrix, "out_bias": out_bias}
+        for key, t in given.items():
+            if t is not None:
+                checked(t, shapes[key], key)
+        st, mt, bt = ((given[key] if given[key] is not None else own(key, shapes[key])) if asked else None
+                      for key, asked in (("out", True), ("out_matrix", matrix), ("out_bias", bias)))
+        check(lib().tg_centroidal(self._h, _ptr(st), _ptr(mt), _ptr(bt)), "centroidal")
+        return Centroidal(st, mt, bt)
 
     @property
     def contact_link_indices(self) -> list:

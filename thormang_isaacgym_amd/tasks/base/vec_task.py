@@ -296,6 +296,12 @@ class VecTask(Env):
         return self.sim.inverse_dynamics(accel=accel, gravity=gravity, velocity=velocity, dofs=dofs, efforts=efforts,
                                          accumulate=accumulate, out=out)
 
+    def centroidal(self, matrix=False, bias=False, out=None, out_matrix=None, out_bias=None):
+        """Centroidal state [N, 16] -- com, com velocity, angular momentum about the com, mass, centroidal inertia --
+        and optionally the centroidal momentum matrix [N, 6, 6 + D] and the momentum-rate bias [N, 6], in one kernel
+        (Sim.centroidal)."""
+        return self.sim.centroidal(matrix=matrix, bias=bias, out=out, out_matrix=out_matrix, out_bias=out_bias)
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)

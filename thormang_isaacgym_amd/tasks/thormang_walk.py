@@ -28,6 +28,14 @@ name) acquires the DOF force tensor: ``dof_forces`` [N,D] and
 simulate, for torque, power or saturation terms a user adds.  The reward keeps
 its own ``stiffness * (target - q)`` torque term; observation and reset do not
 read the tensor either.  The step runs unfused as above.
+
+``env.enableCentroidalState: true`` (optional, default false) adds
+``extras["centroidal"]`` [N,16] after every step -- the whole-body centre of
+mass, its velocity, the angular momentum about it, the mass and the centroidal
+inertia (tgsim.h tg_centroidal) of the state the step returns with, one extra
+kernel launch per step -- for CoM height, capture-point or angular-momentum
+terms a user adds.  Observation, reward and reset do not read it, and the step
+itself is unchanged.
 """
 from __future__ import annotations
 
@@ -100,6 +108,11 @@ class ThormangWalk(VecTask):
         if bool(env.get("enableDofForceSensors", False)):
             self.dof_forces = self.acquire_dof_force_tensor()
             self._contact_extras()
+        # env.enableCentroidalState: com, com velocity, angular momentum, mass and centroidal inertia of the state a
+        # step returns with (tg_centroidal); observation, reward and reset do not use them
+        self.centroidal_state = None
+        if bool(env.get("enableCentroidalState", False)):
+            self.centroidal_state = torch.zeros(N, abi.TG_CENTROIDAL_STATE, device=dev)
         self.reset_idx(torch.arange(N, device=dev))
 
     # ------------------------------------------------------------ creation
@@ -181,6 +194,9 @@ class ThormangWalk(VecTask):
         # extras["dof_force"] [N, D]: the DOF force tensor (env.enableDofForceSensors)
         if self.dof_forces is not None:
             self.extras["dof_force"] = self.dof_forces.to(self.rl_device)
+        # extras["centroidal"] [N, 16]: the centroidal state (env.enableCentroidalState)
+        if getattr(self, "centroidal_state", None) is not None:
+            self.extras["centroidal"] = self.centroidal(out=self.centroidal_state).state.to(self.rl_device)
 
     def step(self, actions):
         if self.dr_randomizations.get("actions", None) or self.dr_randomizations.get("observations", None):
