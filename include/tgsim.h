@@ -72,6 +72,12 @@
  *                            the centroidal inertia, the centroidal momentum matrix
  *                            A_G with h_G = A_G u and the momentum-rate bias A_G' u,
  *                            in the coordinates of tg_jacobians / tg_mass_matrices
+ *   tg_contact_inverse_dynamics
+ *                            no reference counterpart: whole-body inverse dynamics
+ *                            under contact -- the base wrench of tau = H a + h
+ *                            distributed over up to four contact links by least
+ *                            squares, the joint torques that are left and the
+ *                            predicted contact wrenches
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -608,6 +614,85 @@ int tg_centroidal(tg_sim *sim,
                   float *state,    /* [N, TG_CENTROIDAL_STATE] device or NULL */
                   float *matrix,   /* [N, 6, 6+D] device or NULL */
                   float *bias);    /* [N, 6] device or NULL */
+/* Contact-consistent inverse dynamics in one kernel: the joint torques of a
+ * floating-base robot that stands on some of its links -- gravity compensation
+ * for a standing or walking humanoid, the feed-forward of a whole-body
+ * controller -- and the contact wrenches that go with them, from which the
+ * caller reads each foot's vertical load, centre of pressure and friction use.
+ * On demand, stream-ordered, computed from the current root and dof state, the
+ * sim's current gravity, the env's body mass scales and its TG_PROP_ARMATURE
+ * and TG_PROP_EFFORT rows; nothing of the sim is written.  contacts and dofs
+ * are HOST memory, read during the call and not retained (they travel to the
+ * kernel by value in its arguments).
+ *
+ * Let b = H a + h be exactly the tau of tg_inverse_dynamics for the same terms
+ * and accel: the same coordinates, gravity, mass scales and armature.  Contact
+ * k of K is a point fixed on link l_k:
+ *   p_k = o_l + R_l offset_k, offset_k in the link frame (the convention of
+ *         tg_ik_chain.offset), o_l the link's origin;
+ *   r_k = p_k - c_root, c_root the root link's centre of mass;
+ *   Jp_k, the 6 x (6 + D) Jacobian of the point: the linear velocity of p_k
+ *         and the angular velocity of the link, Jv_l - [p_k - c_l]x Jw_l
+ *         stacked on Jw_l from the rows of tg_jacobians (c_l the link's com);
+ *   G_k = Jp_k[:, 0:6]^T = [[1, 0], [[r_k]x, 1]].
+ * Each contact carries a wrench lambda_k = (f_k, n_k): the force and moment
+ * the environment exerts on the robot, world axes, the moment about p_k.  The
+ * call chooses the wrenches that balance the base rows at least weighted cost:
+ *   minimise  sum_k (|f_k|^2 + |n_k|^2 / l^2) / s_k   subject to   sum_k G_k lambda_k = b[0:6]
+ * s_k >= 0 is the per-env load share of contact k (share [N, K]; NULL: all
+ * ones; negative values are taken as 0) and l = moment_arm > 0, in metres: a
+ * moment n costs as much as a force n / l.  In closed form, with
+ * Dm = diag(1, 1, 1, l^2, l^2, l^2):
+ *   A = sum_k s_k G_k Dm G_k^T     (6 x 6; SPD whenever some s_k > 0, G_k being invertible)
+ *   y = A^-1 b[0:6]
+ *   f_k = s_k (y_f + y_n x r_k)
+ *   n_k = s_k l^2 y_n
+ *   tau[6 + d] = b[6 + d] - sum_k Jp_k[:, 6 + d]^T lambda_k   (the armature is already in b)
+ *   tau[0:6]   = b[0:6] - sum_k G_k lambda_k
+ * tau[0:6] is the part of the base wrench that the contacts do not carry: 0 up
+ * to rounding for an env with some s_k > 0.  (The minimiser does not depend on
+ * the point the moments are taken about; the kernel takes them about the
+ * share-weighted mean of the contact points, where A is block diagonal.)
+ *
+ * A contact with s_k = 0 gets a wrench of exactly 0.0, and such an env's other
+ * outputs equal those of a call without that contact: a swing foot.  An env
+ * with every s_k = 0 is airborne: no solve is made, every lambda_k is 0.0 and
+ * tau equals b, the plain inverse dynamics.
+ *
+ * The distribution is a least-squares one.  It knows nothing of unilateral
+ * contact, friction cones or the foot's outline.  The caller judges
+ * feasibility from the returned wrenches (f_z > 0, |f_xy| <= mu f_z, the centre
+ * of pressure (-n_y / f_z, n_x / f_z) inside the sole) and steers it with
+ * share.
+ *
+ * wrench[e, k] = (f_k, n_k).  terms, accel, efforts, dofs, num_dofs and
+ * accumulate mean exactly what they mean in tg_inverse_dynamics, with t =
+ * tau[6 + d] of this call: the clamp to TG_PROP_EFFORT, the limit of 256 DOFs
+ * for efforts, and no other element of efforts is touched.  Every element of
+ * every non-NULL output is written; with fix_base the full layout is written
+ * too.  All lever arms are formed relative to the root link's origin: the
+ * result is bit-identical wherever the env sits on the grid.
+ *
+ * TG_ERR_ARG (message "tg_contact_inverse_dynamics: ...") for a null sim, null
+ * contacts, num_contacts outside 1..TG_CID_MAX_CONTACTS, a link outside [0, L),
+ * a link listed twice, moment_arm not finite or <= 0, tau, wrench and efforts
+ * all NULL, and every argument error of tg_inverse_dynamics on the arguments
+ * the two share (terms outside 0..3, terms == 0 with accel NULL, num_dofs
+ * outside 0..D, dofs NULL with num_dofs > 0, a DOF outside [0, D), a DOF
+ * listed twice, efforts on a model of more than 256 DOFs).  A rejected call
+ * launches nothing.  Every model, run-time (tg_model_jit) ones included. */
+#define TG_CID_MAX_CONTACTS 4          /* both feet and both hands */
+typedef struct tg_contact_frame {      /* HOST, read during the call */
+    int32_t link;
+    float offset[3];                   /* the contact point in the link frame */
+} tg_contact_frame;                    /* 16 bytes */
+int tg_contact_inverse_dynamics(tg_sim *sim, const tg_contact_frame *contacts /* HOST */, int32_t num_contacts,
+                                const float *share,   /* [N, K] device or NULL (= 1) */
+                                float moment_arm, int32_t terms, const float *accel /* [N, 6+D] or NULL */,
+                                float *tau,           /* [N, 6+D] device or NULL */
+                                float *wrench,        /* [N, K, 6] device or NULL */
+                                float *efforts,       /* [N, D] device or NULL */
+                                const int32_t *dofs /* HOST */, int32_t num_dofs, int32_t accumulate);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

@@ -71,6 +71,17 @@ class tg_ik_chain(C.Structure):
     ]
 
 
+TG_CID_MAX_CONTACTS = 4                 # contacts of one tg_contact_inverse_dynamics call
+
+
+class tg_contact_frame(C.Structure):
+    """One contact of tg_contact_inverse_dynamics (tgsim.h): the link and the contact point in its frame."""
+    _fields_ = [("link", C.c_int32), ("offset", C.c_float * 3)]
+
+
+assert C.sizeof(tg_contact_frame) == 16
+
+
 class tg_osc_gains(C.Structure):
     """The gains of tg_osc (tgsim.h): task-space kp / kd, null-space kp_null / kd_null, the damping lambda."""
     _fields_ = [("kp", C.c_float), ("kd", C.c_float), ("kp_null", C.c_float), ("kd_null", C.c_float),

@@ -179,6 +179,18 @@ int launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, 
     }) ? rc : jit_launch_inverse_dynamics(hash, root, dof, mass_scale, props, n, ia, accel, tau, efforts, stream);
 }
 
+int launch_contact_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                                    const float *props, int n, const IdArgs &ia, const CidArgs &ca, const float *share,
+                                    const float *accel, float *tau, float *wrench, float *efforts,
+                                    hipStream_t stream) {
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(contact_inverse_dynamics_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, props,
+                 n, ia, ca, share, accel, tau, wrench, efforts);
+    }) ? rc : jit_launch_contact_inverse_dynamics(hash, root, dof, mass_scale, props, n, ia, ca, share, accel, tau,
+                                                  wrench, efforts, stream);
+}
+
 int launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n, float *state,
                       float *matrix, float *bias, hipStream_t stream) {
     int rc = 0;

@@ -1621,6 +1621,227 @@ __global__ __launch_bounds__(64) void inverse_dynamics_kernel(const float *root,
     }
 }
 
+// Contact-consistent inverse dynamics (tgsim.h tg_contact_inverse_dynamics):
+// b = H a + h as inverse_dynamics_kernel forms it, the K contact wrenches that
+// balance b[0:6] at least weighted cost, and the joint torques that are left.
+// The wrenches are external forces on their links, so by linearity of the
+// inward pass this is the recursive Newton-Euler pass of inverse_dynamics_kernel
+// with one stage more, not two passes.  One wavefront per env:
+//   lanes        forward kinematics, the outward pass and the per-link wrenches
+//                W[l] about the root origin, exactly as inverse_dynamics_kernel
+//   lanes 0..5   the whole-body total of W over the links in link order
+//   every lane   (the same values in each, so nothing is exchanged) the clamped
+//                shares s_k, the contact points p_k = o_l + R_l offset_k and
+//                their share-weighted mean pm; the total's moment about pm.
+//                About pm the 6 x 6 matrix A = sum_k s_k G_k Dm G_k^T of the
+//                header is block diagonal -- sum_k s_k (p_k - pm) = 0 -- and the
+//                minimiser does not depend on the point the moments are taken
+//                about, so the solve is y_f = F / S and a 3 x 3 Cholesky solve
+//                (ik_chol_solve) of sum_k s_k (|r_k|^2 1 - r_k r_k^T + l^2 1) y_n
+//                = N_pm, r_k = p_k - pm; f_k = s_k (y_f + y_n x r_k), n_k = s_k
+//                l^2 y_n, exactly 0.0 for s_k = 0 and for S = 0 (no solve)
+//   lanes 0..5   each wrench, moved to the root origin, subtracted from
+//                W[l_k]; then the subtree sums in descending link order
+//   lane 6 k + i wrench[e, k, i]
+//   lane = DOF   the projection on the joint axis, armature, tau and efforts,
+//                as inverse_dynamics_kernel
+//   lanes 0..5   the base rows: what the contacts leave of the whole body's
+//                force and of its moment about the root com
+// Wave-level syncs only, plain stores, no atomics.
+template <class M>
+__global__ __launch_bounds__(64) void contact_inverse_dynamics_kernel(const float *root, const float *dof,
+                                                                      const float *mass_scale, const float *props,
+                                                                      int n, IdArgs ia, CidArgs ca, const float *share,
+                                                                      const float *accel, float *tau, float *wrench,
+                                                                      float *efforts) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    static_assert(6 * TG_CID_MAX_CONTACTS <= 64, "one lane per wrench component");
+    using JT = JacTables<M>;
+    constexpr int C = 6 + M::ND, MK = TG_CID_MAX_CONTACTS;
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    __shared__ float T[M::NL][12], A[M::NL][3], V[M::NL][9], W[M::NL][6], B[6], LAM[MK][6];
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e, *q = dof + 2 * (size_t)e * M::ND;
+    const float *ac = accel ? accel + (size_t)e * C : nullptr;
+    const bool vel = (ia.terms & TG_ID_VELOCITY) != 0;
+    const V3 zero = v3(0.f, 0.f, 0.f);
+    const int K = ca.K < MK ? ca.K : MK;
+    // the shares, ahead of the chain of passes; negative (and NaN) ones count as 0
+    float s[MK];
+#pragma unroll
+    for (int k = 0; k < MK; ++k) s[k] = k < K ? (share ? fmaxf(share[(size_t)e * K + k], 0.f) : 1.f) : 0.f;
+    fk_root_relative<M>(r, q, lane, T, A);
+    // the root link's com relative to its origin, world axes
+    V3 c0;
+    {
+        M3 R0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R0.a[k] = T[0][k];
+        c0 = mul(R0, v3(M::link_inertia[0][1], M::link_inertia[0][2], M::link_inertia[0][3]));
+    }
+    constexpr int NP = (M::NL + 63) / 64;   // links per lane
+    for (int lev = 0; lev <= M::NDEPTH; ++lev) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int l = lane + 64 * p;
+            if (l >= M::NL || M::link_depth[l] != lev) continue;
+            const int pl = M::link_parent[l];
+            V3 w, al, ao;
+            if (pl < 0) {
+                w = vel ? v3(r[10], r[11], r[12]) : zero;
+                al = ac ? v3(ac[3], ac[4], ac[5]) : zero;
+                V3 acom = ac ? v3(ac[0], ac[1], ac[2]) : zero;
+                if (ia.terms & TG_ID_GRAVITY) acom = acom - v3(ia.g[0], ia.g[1], ia.g[2]);
+                ao = acom - cross(al, c0) - cross(w, cross(w, c0));
+            } else {
+                const V3 wp = v3(V[pl][0], V[pl][1], V[pl][2]), alp = v3(V[pl][3], V[pl][4], V[pl][5]);
+                const V3 rr = v3(T[l][9], T[l][10], T[l][11]) - v3(T[pl][9], T[pl][10], T[pl][11]);
+                const int d = M::link_dof[l];
+                const float qd = d >= 0 && vel ? q[2 * d + 1] : 0.f, qdd = d >= 0 && ac ? ac[6 + d] : 0.f;
+                const V3 a = v3(A[l][0], A[l][1], A[l][2]);
+                w = wp;
+                al = alp;
+                ao = v3(V[pl][6], V[pl][7], V[pl][8]) + cross(alp, rr) + cross(wp, cross(wp, rr));
+                if (M::link_jtype[l] == TG_JOINT_REVOLUTE) {
+                    w = w + qd * a;
+                    al = al + qdd * a + cross(wp, qd * a);
+                } else if (M::link_jtype[l] == TG_JOINT_PRISMATIC) {
+                    ao = ao + qdd * a + 2.f * cross(wp, qd * a);
+                }
+            }
+            V[l][0] = w.x; V[l][1] = w.y; V[l][2] = w.z;
+            V[l][3] = al.x; V[l][4] = al.y; V[l][5] = al.z;
+            V[l][6] = ao.x; V[l][7] = ao.y; V[l][8] = ao.z;
+        }
+        wsync();
+    }
+    // every link's force and its moment about the root origin, mass-scaled
+    for (int l = lane; l < M::NL; l += 64) {
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const float *li = M::link_inertia[l];
+        const float sc = mass_scale ? mass_scale[(size_t)e * M::NL + l] : 1.f;
+        const V3 rc = mul(R, v3(li[1], li[2], li[3])), c = v3(T[l][9], T[l][10], T[l][11]) + rc;
+        float I[6];
+        sym_rot(li + 4, transpose(R), I);   // R I R^T
+        const V3 w = v3(V[l][0], V[l][1], V[l][2]), al = v3(V[l][3], V[l][4], V[l][5]);
+        const V3 acom = v3(V[l][6], V[l][7], V[l][8]) + cross(al, rc) + cross(w, cross(w, rc));
+        const V3 f = (sc * li[0]) * acom;
+        const V3 nn = sc * (symmul(I, al) + cross(w, symmul(I, w))) + cross(c, f);
+        W[l][0] = f.x; W[l][1] = f.y; W[l][2] = f.z;
+        W[l][3] = nn.x; W[l][4] = nn.y; W[l][5] = nn.z;
+    }
+    wsync();
+    // the whole body's force and moment about the root origin
+    if (lane < 6) {
+        float t = W[0][lane];
+        for (int l = 1; l < M::NL; ++l) t += W[l][lane];
+        B[lane] = t;
+    }
+    wsync();
+    // the distribution, the same in every lane
+    V3 p[MK], f[MK], nk = zero;
+    float S = 0.f;
+    V3 pm = zero;
+#pragma unroll
+    for (int k = 0; k < MK; ++k) {
+        p[k] = zero;
+        f[k] = zero;
+        if (k >= K) continue;
+        const int l = ca.c[k].link;
+        M3 R;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R.a[i] = T[l][i];
+        p[k] = v3(T[l][9], T[l][10], T[l][11]) + mul(R, v3(ca.c[k].offset[0], ca.c[k].offset[1], ca.c[k].offset[2]));
+        S += s[k];
+        pm = pm + s[k] * p[k];
+    }
+    if (S > 0.f) {
+        pm = (1.0f / S) * pm;
+        const V3 F = v3(B[0], B[1], B[2]);
+        const V3 Nm = v3(B[3], B[4], B[5]) - cross(pm, F);   // the moment about pm
+        // lower triangle by rows: xx, yx, yy, zx, zy, zz
+        const float d0 = S * ca.arm2;
+        float g[6] = {d0, 0.f, d0, 0.f, 0.f, d0};
+#pragma unroll
+        for (int k = 0; k < MK; ++k) {
+            if (k >= K) continue;
+            const V3 rk = p[k] - pm;
+            const float r2 = dot(rk, rk);
+            g[0] += s[k] * (r2 - rk.x * rk.x);
+            g[1] -= s[k] * (rk.y * rk.x);
+            g[2] += s[k] * (r2 - rk.y * rk.y);
+            g[3] -= s[k] * (rk.z * rk.x);
+            g[4] -= s[k] * (rk.z * rk.y);
+            g[5] += s[k] * (r2 - rk.z * rk.z);
+        }
+        const float bn[3] = {Nm.x, Nm.y, Nm.z};
+        float y[3];
+        ik_chol_solve<3>(g, bn, y);
+        const V3 yf = (1.0f / S) * F, yn = v3(y[0], y[1], y[2]);
+        nk = ca.arm2 * yn;
+#pragma unroll
+        for (int k = 0; k < MK; ++k)
+            if (k < K && s[k] > 0.f) f[k] = s[k] * (yf + cross(yn, p[k] - pm));
+    }
+    if (lane < 6) {
+        // lane t carries float t of every wrench about the root origin, then of the subtree sums
+#pragma unroll
+        for (int k = 0; k < MK; ++k) {
+            if (k >= K) continue;
+            const V3 m = s[k] > 0.f ? s[k] * nk : zero;
+            const V3 mo = m + cross(p[k], f[k]);
+            const float o[6] = {f[k].x, f[k].y, f[k].z, mo.x, mo.y, mo.z}, w6[6] = {f[k].x, f[k].y, f[k].z, m.x, m.y, m.z};
+            float vo = o[0], vw = w6[0];
+#pragma unroll
+            for (int i = 1; i < 6; ++i) {
+                vo = lane == i ? o[i] : vo;
+                vw = lane == i ? w6[i] : vw;
+            }
+            W[ca.c[k].link][lane] -= vo;
+            LAM[k][lane] = vw;
+        }
+#pragma unroll
+        for (int k = M::NL - 1; k >= 1; --k) W[M::link_parent[k]][lane] += W[k][lane];
+    }
+    wsync();
+    if (wrench && lane < 6 * K) wrench[((size_t)e * K) * 6 + lane] = LAM[lane / 6][lane % 6];
+    float *to = tau ? tau + (size_t)e * C : nullptr;
+    for (int d = lane; d < M::ND; d += 64) {
+        const int j = JT::dof_link.v[d];
+        const V3 a = v3(A[j][0], A[j][1], A[j][2]), fj = v3(W[j][0], W[j][1], W[j][2]);
+        float t;
+        if (M::link_jtype[j] == TG_JOINT_PRISMATIC)
+            t = dot(a, fj);
+        else
+            t = dot(a, v3(W[j][3], W[j][4], W[j][5]) - cross(v3(T[j][9], T[j][10], T[j][11]), fj));
+        if (ac) t += props[((size_t)TG_PROP_ARMATURE * n + e) * M::ND + d] * ac[6 + d];
+        if (to) to[6 + d] = t;
+        if (efforts && d < 32 * TG_ID_MASK_WORDS && ((ia.mask[d >> 5] >> (d & 31)) & 1u)) {
+            const float lim = props[((size_t)TG_PROP_EFFORT * n + e) * M::ND + d];
+            float *o = efforts + (size_t)e * M::ND + d;
+            const float sum = ia.accumulate ? *o + t : t;
+            *o = fminf(fmaxf(sum, -lim), lim);
+        }
+    }
+    if (to && lane < 6) {
+        const V3 fr = v3(W[0][0], W[0][1], W[0][2]);
+        const V3 nc = v3(W[0][3], W[0][4], W[0][5]) - cross(c0, fr);   // the moment about the root com
+        const float o[6] = {fr.x, fr.y, fr.z, nc.x, nc.y, nc.z};
+        float v = o[0];
+#pragma unroll
+        for (int k = 1; k < 6; ++k) v = lane == k ? o[k] : v;
+        to[lane] = v;
+    }
+}
+
 // Centroidal quantities (tgsim.h tg_centroidal): the whole-body centre of mass
 // c, its velocity, the angular momentum k about it, the total mass M and the
 // centroidal inertia I_G into state [N, 16]; the centroidal momentum matrix A

@@ -34,7 +34,7 @@
 namespace tg {
 namespace {
 
-enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, K_ID, K_CENTROIDAL, NK };
+enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, K_ID, K_CENTROIDAL, K_CID, NK };
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, false, tg::NoPost>",
@@ -47,6 +47,7 @@ const char *const KERNEL_EXPR[NK] = {
     "tg::osc_kernel<TgJitModel>",
     "tg::inverse_dynamics_kernel<TgJitModel>",
     "tg::centroidal_kernel<TgJitModel>",
+    "tg::contact_inverse_dynamics_kernel<TgJitModel>",
 };
 // the per-model launch figures the host needs, read back from the module
 // (tgjit_meta, same order)
@@ -155,7 +156,7 @@ int compile(const std::string &src, const std::string &incdir, JitCode &out, std
     return 0;
 }
 
-// cache file: "TGJIT6\n", one lowered name per line, then the code object
+// cache file: "TGJIT7\n", one lowered name per line, then the code object
 bool cache_load(const std::string &path, JitCode &out) {
     std::string s;
     if (!read_file(path, s)) return false;
@@ -168,7 +169,7 @@ bool cache_load(const std::string &path, JitCode &out) {
         return true;
     };
     std::string magic;
-    if (!line(magic) || magic != "TGJIT6") return false;
+    if (!line(magic) || magic != "TGJIT7") return false;
     for (int k = 0; k < NK; ++k)
         if (!line(out.names[k]) || out.names[k].empty()) return false;
     if (pos >= s.size()) return false;
@@ -181,7 +182,7 @@ void cache_store(const std::string &path, const JitCode &c) {
     {
         std::ofstream f(tmp, std::ios::binary);
         if (!f) return;
-        f << "TGJIT6\n";
+        f << "TGJIT7\n";
         for (int k = 0; k < NK; ++k) f << c.names[k] << "\n";
         f.write(c.code.data(), (std::streamsize)c.code.size());
         if (!f) return;
@@ -358,6 +359,18 @@ int jit_launch_inverse_dynamics(uint64_t hash, const float *root, const float *d
     IdArgs aa = ia;
     void *args[] = {&root, &dof, &mass_scale, &props, &n, &aa, &accel, &tau, &efforts};
     return launch(L->f[K_ID], (unsigned)n, 64, 0, stream, args);
+}
+
+int jit_launch_contact_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                                        const float *props, int n, const IdArgs &ia, const CidArgs &ca,
+                                        const float *share, const float *accel, float *tau, float *wrench,
+                                        float *efforts, hipStream_t stream) {
+    JitLoaded *L = find(hash);
+    if (!L) return TG_ERR_MODEL;
+    IdArgs aa = ia;
+    CidArgs cc = ca;
+    void *args[] = {&root, &dof, &mass_scale, &props, &n, &aa, &cc, &share, &accel, &tau, &wrench, &efforts};
+    return launch(L->f[K_CID], (unsigned)n, 64, 0, stream, args);
 }
 
 int jit_launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n,

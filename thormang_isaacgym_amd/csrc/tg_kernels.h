@@ -32,6 +32,13 @@ struct IdArgs {
     int terms, accumulate;
     uint32_t mask[TG_ID_MASK_WORDS];
 };
+// the contacts of a tg_contact_inverse_dynamics call, passed to contact_inverse_dynamics_kernel by value beside
+// its IdArgs: the K contact frames and the squared moment arm
+struct CidArgs {
+    tg_contact_frame c[TG_CID_MAX_CONTACTS];
+    int K;
+    float arm2;
+};
 
 // optional Gogoro pre-physics prologue of the compose launch (tg_gogoro_step)
 struct GogoroPre {
@@ -216,6 +223,12 @@ int launch_osc(uint64_t hash, const float *root, const float *dof, const float *
 int launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                             const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
                             float *efforts, hipStream_t stream);
+// contact-consistent inverse dynamics: tau [N, 6 + D], the contact wrenches [N, K, 6] and / or efforts [N, D]
+// (contact_inverse_dynamics_kernel; tgsim.h tg_contact_inverse_dynamics)
+int launch_contact_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                                    const float *props, int n, const IdArgs &ia, const CidArgs &ca, const float *share,
+                                    const float *accel, float *tau, float *wrench, float *efforts,
+                                    hipStream_t stream);
 // centroidal state [N, 16], momentum matrix [N, 6, 6 + D] and momentum-rate bias [N, 6], each optional
 // (centroidal_kernel; tgsim.h tg_centroidal)
 int launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n, float *state,
@@ -259,6 +272,10 @@ int jit_launch_osc(uint64_t hash, const float *root, const float *dof, const flo
 int jit_launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                                 const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
                                 float *efforts, hipStream_t stream);
+int jit_launch_contact_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
+                                        const float *props, int n, const IdArgs &ia, const CidArgs &ca,
+                                        const float *share, const float *accel, float *tau, float *wrench,
+                                        float *efforts, hipStream_t stream);
 int jit_launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n,
                           float *state, float *matrix, float *bias, hipStream_t stream);
 

@@ -813,25 +813,26 @@ int tg_osc(tg_sim *s, const tg_ik_chain *chains, int32_t num_chains, const float
     return TG_OK;
 }
 
-int tg_inverse_dynamics(tg_sim *s, int32_t terms, const float *accel, float *tau, float *efforts,
-                        const int32_t *dofs, int32_t num_dofs, int32_t accumulate) {
-    if (!s) return fail(TG_ERR_ARG, "tg_inverse_dynamics: null tg_sim");
+// the checks tg_inverse_dynamics and tg_contact_inverse_dynamics share, and the IdArgs they fill; fn: the call's
+// name for the message
+static int check_id_terms(const char *fn, int32_t terms, const float *accel) {
     if (terms < 0 || terms > (TG_ID_GRAVITY | TG_ID_VELOCITY))
-        return fail(TG_ERR_ARG, "tg_inverse_dynamics: terms %d outside 0..%d", terms, TG_ID_GRAVITY | TG_ID_VELOCITY);
-    if (terms == 0 && !accel) return fail(TG_ERR_ARG, "tg_inverse_dynamics: no terms and no accel");
-    if (!tau && !efforts) return fail(TG_ERR_ARG, "tg_inverse_dynamics: tau and efforts are both null");
-    if (num_dofs < 0 || num_dofs > s->D)
-        return fail(TG_ERR_ARG, "tg_inverse_dynamics: num_dofs %d outside 0..%d", num_dofs, s->D);
-    if (num_dofs > 0 && !dofs) return fail(TG_ERR_ARG, "tg_inverse_dynamics: null dofs with num_dofs %d", num_dofs);
+        return fail(TG_ERR_ARG, "%s: terms %d outside 0..%d", fn, terms, TG_ID_GRAVITY | TG_ID_VELOCITY);
+    if (terms == 0 && !accel) return fail(TG_ERR_ARG, "%s: no terms and no accel", fn);
+    return TG_OK;
+}
+static int check_id_dofs(const tg_sim *s, const char *fn, int32_t terms, const float *efforts, const int32_t *dofs,
+                         int32_t num_dofs, int32_t accumulate, tg::IdArgs &ia) {
+    if (num_dofs < 0 || num_dofs > s->D) return fail(TG_ERR_ARG, "%s: num_dofs %d outside 0..%d", fn, num_dofs, s->D);
+    if (num_dofs > 0 && !dofs) return fail(TG_ERR_ARG, "%s: null dofs with num_dofs %d", fn, num_dofs);
     constexpr int MASK_BITS = 32 * tg::TG_ID_MASK_WORDS;
     if (efforts && s->D > MASK_BITS)
-        return fail(TG_ERR_ARG, "tg_inverse_dynamics: efforts of a model with %d DOFs, more than %d", s->D, MASK_BITS);
-    tg::IdArgs ia{};
+        return fail(TG_ERR_ARG, "%s: efforts of a model with %d DOFs, more than %d", fn, s->D, MASK_BITS);
     for (int i = 0; i < num_dofs; ++i) {
         const int d = dofs[i];
-        if (d < 0 || d >= s->D) return fail(TG_ERR_ARG, "tg_inverse_dynamics: DOF %d outside [0, %d)", d, s->D);
+        if (d < 0 || d >= s->D) return fail(TG_ERR_ARG, "%s: DOF %d outside [0, %d)", fn, d, s->D);
         for (int j = 0; j < i; ++j)
-            if (dofs[j] == d) return fail(TG_ERR_ARG, "tg_inverse_dynamics: DOF %d appears twice", d);
+            if (dofs[j] == d) return fail(TG_ERR_ARG, "%s: DOF %d appears twice", fn, d);
         if (d < MASK_BITS) ia.mask[d >> 5] |= 1u << (d & 31);   // (beyond it only without efforts: nothing reads the mask)
     }
     if (num_dofs == 0)   // every DOF
@@ -839,11 +840,54 @@ int tg_inverse_dynamics(tg_sim *s, int32_t terms, const float *accel, float *tau
     memcpy(ia.g, s->gravity, sizeof ia.g);
     ia.terms = terms;
     ia.accumulate = accumulate != 0;
+    return TG_OK;
+}
+
+int tg_inverse_dynamics(tg_sim *s, int32_t terms, const float *accel, float *tau, float *efforts,
+                        const int32_t *dofs, int32_t num_dofs, int32_t accumulate) {
+    if (!s) return fail(TG_ERR_ARG, "tg_inverse_dynamics: null tg_sim");
+    const char *fn = "tg_inverse_dynamics";
+    if (int rc = check_id_terms(fn, terms, accel)) return rc;
+    if (!tau && !efforts) return fail(TG_ERR_ARG, "%s: tau and efforts are both null", fn);
+    tg::IdArgs ia{};
+    if (int rc = check_id_dofs(s, fn, terms, efforts, dofs, num_dofs, accumulate, ia)) return rc;
     DeviceGuard dg(s->device);
     win_touch(s);
     if (int rc = tg::launch_inverse_dynamics(s->hash, s->root, s->dof, s->mass_scale, s->props, (int)s->N, ia, accel, tau,
                                              efforts, s->stream))
         return fail(rc, "tg_inverse_dynamics: launch failed");
+    return TG_OK;
+}
+
+int tg_contact_inverse_dynamics(tg_sim *s, const tg_contact_frame *contacts, int32_t num_contacts, const float *share,
+                                float moment_arm, int32_t terms, const float *accel, float *tau, float *wrench,
+                                float *efforts, const int32_t *dofs, int32_t num_dofs, int32_t accumulate) {
+    const char *fn = "tg_contact_inverse_dynamics";
+    if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
+    if (!contacts) return fail(TG_ERR_ARG, "%s: null contacts", fn);
+    if (num_contacts < 1 || num_contacts > TG_CID_MAX_CONTACTS)
+        return fail(TG_ERR_ARG, "%s: num_contacts %d outside 1..%d", fn, num_contacts, TG_CID_MAX_CONTACTS);
+    tg::CidArgs ca{};
+    for (int k = 0; k < num_contacts; ++k) {
+        const int l = contacts[k].link;
+        if (l < 0 || l >= s->L) return fail(TG_ERR_ARG, "%s: contact %d: link %d outside [0, %d)", fn, k, l, s->L);
+        for (int j = 0; j < k; ++j)
+            if (contacts[j].link == l) return fail(TG_ERR_ARG, "%s: link %d appears twice", fn, l);
+        ca.c[k] = contacts[k];
+    }
+    if (!(moment_arm > 0.f) || !std::isfinite(moment_arm))
+        return fail(TG_ERR_ARG, "%s: moment_arm %g is not a finite number > 0", fn, (double)moment_arm);
+    if (int rc = check_id_terms(fn, terms, accel)) return rc;
+    if (!tau && !wrench && !efforts) return fail(TG_ERR_ARG, "%s: tau, wrench and efforts are all null", fn);
+    tg::IdArgs ia{};
+    if (int rc = check_id_dofs(s, fn, terms, efforts, dofs, num_dofs, accumulate, ia)) return rc;
+    ca.K = num_contacts;
+    ca.arm2 = moment_arm * moment_arm;
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_contact_inverse_dynamics(s->hash, s->root, s->dof, s->mass_scale, s->props, (int)s->N, ia,
+                                                     ca, share, accel, tau, wrench, efforts, s->stream))
+        return fail(rc, "%s: launch failed", fn);
     return TG_OK;
 }
 

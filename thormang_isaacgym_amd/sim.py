@@ -138,6 +138,7 @@ def _ptr(t: torch.Tensor | None):
 
 
 Centroidal = namedtuple("Centroidal", ["state", "matrix", "bias"])   # what Sim.centroidal returns
+ContactDynamics = namedtuple("ContactDynamics", ["tau", "wrench"])   # what Sim.contact_inverse_dynamics returns
 
 
 class Sim:
@@ -596,6 +597,86 @@ class Sim:
         check(lib().tg_inverse_dynamics(self._h, terms, _ptr(accel), _ptr(out), _ptr(efforts), arr, len(idx),
                                         1 if accumulate else 0), "inverse_dynamics")
         return out
+
+    def contact_frame(self, link, offset=(0.0, 0.0, 0.0)) -> abi.tg_contact_frame:
+        """One contact of ``contact_inverse_dynamics`` (tgsim.h
+        tg_contact_frame): the ``link`` in contact, by name or index, and the
+        contact point ``offset`` in the link frame (the convention of
+        ``ik_chain``)."""
+        l = self._name_index("link", link)
+        if not 0 <= l < self.L:
+            raise ValueError(f"link {link!r} outside [0, {self.L})")
+        c = abi.tg_contact_frame()
+        c.link = l
+        c.offset[:] = [float(v) for v in offset]
+        return c
+
+    def contact_inverse_dynamics(self, contacts, share: torch.Tensor | None = None, accel: torch.Tensor | None = None,
+                                 gravity: bool = True, velocity: bool = True, moment_arm: float = 0.1,
+                                 out: torch.Tensor | None = None, wrench: torch.Tensor | None = None, dofs=None,
+                                 efforts: torch.Tensor | None = None,
+                                 accumulate: bool = False) -> "ContactDynamics":
+        """Inverse dynamics of the floating-base robot standing on the K
+        ``contacts`` (``contact_frame``, at most 4), in one kernel launch
+        (tgsim.h tg_contact_inverse_dynamics).  With ``b = H a + h`` exactly
+        what ``inverse_dynamics`` returns for the same ``accel``, ``gravity``
+        and ``velocity``, the base rows ``b[:, :6]`` are distributed over the
+        contacts as the wrenches (force, moment about the contact point; world
+        axes, acting on the robot) of least cost ``sum_k (|f_k|^2 + |n_k|^2 /
+        moment_arm^2) / share_k`` -- a least-squares distribution that knows
+        nothing of unilateral contact, friction cones or the foot's outline;
+        judge the returned wrenches and steer them with ``share`` [N, K] (None:
+        ones; 0 unloads a contact exactly, a swing foot; an env with all zeros
+        is airborne and gets the plain inverse dynamics).  Returns
+        ``ContactDynamics(tau, wrench)``: ``tau`` [N, 6 + D] with the joint
+        torques that are left in ``tau[:, 6:]`` and the base wrench the
+        contacts do not carry (0 up to rounding) in ``tau[:, :6]``, ``wrench``
+        [N, K, 6].  They are ``out`` / ``wrench`` if given, else tensors owned
+        by the sim that the next call (with as many contacts) overwrites.
+        ``efforts``, ``dofs`` and ``accumulate`` as in ``inverse_dynamics``:
+        ``contact_inverse_dynamics(feet, efforts=sim.dof_actuation)`` is
+        gravity compensation of the standing robot."""
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        contacts = list(contacts)
+        K = len(contacts)
+        if not 1 <= K <= abi.TG_CID_MAX_CONTACTS:
+            raise ValueError(f"contact_inverse_dynamics takes 1..{abi.TG_CID_MAX_CONTACTS} contacts, got {K}")
+        contacts = [c if isinstance(c, abi.tg_contact_frame) else self.contact_frame(c) for c in contacts]
+        N, C_ = self.num_envs, 6 + self.D
+        for t, shape, what in ((share, (N, K), "share"), (accel, (N, C_), "accel"), (efforts, (N, self.D), "efforts"),
+                               (out, (N, C_), "out"), (wrench, (N, K, 6), "wrench")):
+            if t is not None:
+                checked(t, shape, what)
+        own = getattr(self, "_cid_out", None)
+        if own is None:
+            own = self._cid_out = {}
+        if out is None:
+            if "tau" not in own:
+                own["tau"] = torch.zeros(N, C_, dtype=torch.float32, device=self.device)
+            out = own["tau"]
+        if wrench is None:
+            if K not in own:
+                own[K] = torch.zeros(N, K, 6, dtype=torch.float32, device=self.device)
+            wrench = own[K]
+        terms = (abi.TG_ID_GRAVITY if gravity else 0) | (abi.TG_ID_VELOCITY if velocity else 0)
+        if terms == 0 and accel is None:
+            raise ValueError("contact_inverse_dynamics without gravity, velocity and accel has nothing to compute")
+        idx = [] if dofs is None else [self._name_index("dof", x) for x in dofs]
+        if dofs is not None and not idx:
+            raise ValueError("dofs is empty; pass None for every DOF")
+        arr = (C.c_int32 * len(idx))(*idx) if idx else None
+        frames = (abi.tg_contact_frame * K)(*contacts)
+        check(lib().tg_contact_inverse_dynamics(self._h, frames, K, _ptr(share), float(moment_arm), terms, _ptr(accel),
+                                                _ptr(out), _ptr(wrench), _ptr(efforts), arr, len(idx),
+                                                1 if accumulate else 0), "contact_inverse_dynamics")
+        return ContactDynamics(out, wrench)
 
     def centroidal(self, matrix: bool = False, bias: bool = False, out: torch.Tensor | None = None,
                    out_matrix: torch.Tensor | None = None, out_bias: torch.Tensor | None = None) -> "Centroidal":
