@@ -46,6 +46,11 @@
  *   tg_set_dof_force_tensor  acquire_dof_force_tensor / refresh_dof_force_tensor
  *                            (tasks/MA_OP3.py:91,96), with
  *                            enable_actor_dof_force_sensors (:275) implied
+ *   tg_set_force_sensor_tensor
+ *                            acquire_force_sensor_tensor /
+ *                            refresh_force_sensor_tensor, with
+ *                            create_asset_force_sensor implied
+ *                            (tasks/humanoid.py:80,167-168,243)
  *   tg_jacobians             acquire_jacobian_tensor / refresh_jacobian_tensors
  *                            (tasks/gogoro/gogoro.py:108-114,396-397,507, the
  *                            rider's hand IK; tasks/franka_cube_stack.py:389-393,
@@ -693,6 +698,57 @@ int tg_contact_inverse_dynamics(tg_sim *sim, const tg_contact_frame *contacts /*
                                 float *wrench,        /* [N, K, 6] device or NULL */
                                 float *efforts,       /* [N, D] device or NULL */
                                 const int32_t *dofs /* HOST */, int32_t num_dofs, int32_t accumulate);
+/* acquire_force_sensor_tensor (with create_asset_force_sensor implied): the
+ * measured counterpart of the wrenches tg_contact_inverse_dynamics predicts.
+ * Up to TG_FS_MAX_SENSORS sensors per env; sensor k is the point
+ *   p_k = o_l + R_l offset_k
+ * on link l_k, the convention of tg_contact_frame and tg_ik_chain.offset, and
+ * the same link may carry several sensors at different offsets.  The sensor
+ * array is read during the call and copied.  out [N, S, 6] device,
+ * caller-owned, kept alive by the caller: out[e, k] = (f, n), newtons and
+ * newton metres, the GROUND REACTION on the sensor's link -- the force the
+ * ground exerts on the link's collision shapes and its moment about p_k.  It
+ * is not IsaacGym's joint-transmitted constraint force: there is no gravity
+ * or inertial part in it and nothing from the links further down the chain.
+ *
+ * Written in full by every later tg_simulate and averaged over that call's
+ * substeps.  Per substep of length h, over the rows j of the shapes on link
+ * l_k -- the normal rows, the two patch-friction rows and the torsion row --
+ * with lambda_j the row's stored-velocity multiplier, d_j its direction, x_j
+ * its point of application (the support point of a normal row, the patch's
+ * friction anchor of a friction row; the torsion row has d_j = 0) and t_j the
+ * torsion row's pure moment (the patch normal; 0 for every other row):
+ *   f = (1 / h) sum_j lambda_j d_j
+ *   n = (1 / h) sum_j lambda_j ((x_j - p_k) x d_j + t_j)
+ * p_k is posed from the state the substep starts from, as the rows are.  f is
+ * the very sum the net contact force tensor holds for the link (bit for bit
+ * in TG_ENV_SPACE); the moment is new, and the torsion row, which carries no
+ * force, enters it.
+ *
+ * space: TG_ENV_SPACE gives world axes, the convention of the wrench output of
+ * tg_contact_inverse_dynamics; TG_LOCAL_SPACE the link's own axes, rotated per
+ * substep with the R_l the substep starts from -- how IsaacGym's sensors read,
+ * and the centre of pressure (-n_y / f_z, n_x / f_z) of a sole whose normal is
+ * the link's z then comes out in sole coordinates whatever the yaw.
+ *
+ * A sensor on a link without collision shapes reads zeros, and so does every
+ * sensor after a simulate with 0 substeps.  The call zero-fills out,
+ * stream-ordered; the tensor then holds the last simulate's values until the
+ * next one, a reset does not clear it, and refresh_force_sensor_tensor has
+ * nothing to do.  out == NULL or num_sensors == 0 turns it off.  It works
+ * together with the net contact force and DOF force tensors (one launch for
+ * any combination).  While it is on, the task steps (tg_walk_step,
+ * tg_gogoro_step, tg_paper_step) run their post-physics as a separate launch
+ * after the last simulate; the states never depend on it.
+ *
+ * TG_ERR_ARG (message "tg_set_force_sensor_tensor: ...") for a null sim,
+ * num_sensors outside 0..TG_FS_MAX_SENSORS, null sensors with num_sensors > 0,
+ * a link outside [0, L), a non-finite offset, space outside {0, 1} and a
+ * non-null out with num_sensors == 0; TG_ERR_MODEL for a model from
+ * tg_model_jit.  A rejected call changes nothing. */
+#define TG_FS_MAX_SENSORS 8
+int tg_set_force_sensor_tensor(tg_sim *sim, const tg_contact_frame *sensors /* HOST */, int32_t num_sensors,
+                               int32_t space /* TG_ENV_SPACE | TG_LOCAL_SPACE */, float *out /* [N, S, 6] device */);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

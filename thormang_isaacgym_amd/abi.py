@@ -81,6 +81,9 @@ class tg_contact_frame(C.Structure):
 
 assert C.sizeof(tg_contact_frame) == 16
 
+TG_FS_MAX_SENSORS = 8                   # sensors of tg_set_force_sensor_tensor (they are tg_contact_frames too)
+TG_ENV_SPACE, TG_LOCAL_SPACE = 0, 1     # axes of per-link vectors (tgsim.h)
+
 
 class tg_osc_gains(C.Structure):
     """The gains of tg_osc (tgsim.h): task-space kp / kd, null-space kp_null / kd_null, the damping lambda."""

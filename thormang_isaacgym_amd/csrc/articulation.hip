@@ -40,7 +40,12 @@ static int compiled_launch(uint64_t hash, const StepArgs &a, const typename P::A
 
 int launch_step(uint64_t hash, const StepArgs &a, const StepPost &post, hipStream_t stream, hipEvent_t ev_begin,
                 hipEvent_t ev_end) {
-    int rc = 0;
+    int rc = 1;
+    // (the force sensor export is declined, 1, by a model without contact
+    // rows: it has nothing to read and takes the other exports' kernel)
+    if (post.fs && !post.fused())
+        rc = compiled_launch<NoPostFS>(hash, a, {post.cf, post.df, post.fs, post.fr}, stream, ev_begin, ev_end);
+    if (rc != 1) return rc != TG_OTHER_UNIT ? rc : TG_ERR_MODEL;
     if (post.walk) rc = compiled_launch<WalkPost>(hash, a, *post.walk, stream, ev_begin, ev_end);
     else if (post.gogoro) rc = compiled_launch<GogoroPost>(hash, a, *post.gogoro, stream, ev_begin, ev_end);
     else if (post.paper) rc = compiled_launch<PaperPost>(hash, a, *post.paper, stream, ev_begin, ev_end);
@@ -51,7 +56,7 @@ int launch_step(uint64_t hash, const StepArgs &a, const StepPost &post, hipStrea
     // the run-time (hipRTC) models have the plain step only: no fused epilogue
     // (the caller falls back), no export
     if (post.fused()) return jit_has(hash) ? 1 : TG_ERR_MODEL;
-    if (post.cf || post.df) return TG_ERR_MODEL;
+    if (post.cf || post.df || post.fs) return TG_ERR_MODEL;
     return jit_launch_step(hash, a, stream, ev_begin, ev_end);
 }
 

@@ -86,6 +86,12 @@ template <> struct StepVariant<NoPostCF> : AnyStep {
     template <class M> static constexpr bool eligible = M::NROWS > 0;
     using Fallback = NoPost;
 };
+// the force sensor export (NoPostFS, fs [N, S, 6], with cf and df when they
+// are not null): for every model with contact rows; launch_step sends a model
+// without any down the other exports' path (the tensor keeps its zeros)
+template <> struct StepVariant<NoPostFS> : AnyStep {
+    template <class M> static constexpr bool eligible = M::NROWS > 0;
+};
 // the fused walk epilogue is instantiated for the lane-pair (humanoid-size)
 // trees on flat ground only
 template <> struct StepVariant<WalkPost> : AnyStep {
@@ -151,7 +157,7 @@ static int unit_launch(uint64_t hash, const StepArgs &a, const typename P::Args 
 
 // the humanoid unit's entry (articulation_tree.hip instantiates it for every
 // post policy of the list)
-#define TG_FOR_EACH_POST(X) X(NoPost) X(NoPostCF) X(NoPostDF) X(WalkPost) X(GogoroPost) X(PaperPost)
+#define TG_FOR_EACH_POST(X) X(NoPost) X(NoPostCF) X(NoPostDF) X(NoPostFS) X(WalkPost) X(GogoroPost) X(PaperPost)
 template <class P>
 int tree_launch(uint64_t hash, const StepArgs &a, const typename P::Args &pa, hipStream_t stream, hipEvent_t ev_begin,
                 hipEvent_t ev_end);

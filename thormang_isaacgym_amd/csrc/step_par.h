@@ -644,6 +644,58 @@ template <int N> struct DFAcc {
 };
 template <> struct DFAcc<0> {};
 
+// NoPost that exports the force sensor tensor (tg_set_force_sensor_tensor):
+// fs [N, S, 6], per sensor (a link and a point in its frame) the ground's
+// force on the link and its moment about the sensor point, in world axes or
+// the link's own, averaged over the launch's substeps.  The one policy carries
+// the other two exports' pointers as well, so that any combination of the
+// three is one launch: a null cf, df or fs skips that tensor's stores.  A
+// policy without an FS member exports nothing (PostFS), so every other
+// instantiation is compiled exactly as before.
+struct NoPostFS : NoPost {
+    struct Args {
+        float *cf;
+        float *df;
+        float *fs;
+        FsFrames fr;
+    };
+    static constexpr bool CF = true;
+    static constexpr bool DF = true;
+    static constexpr bool FS = true;
+};
+template <class P, class = void> struct PostFS {
+    static constexpr bool value = false;
+};
+template <class P> struct PostFS<P, decltype((void)P::FS)> {
+    static constexpr bool value = P::FS;
+};
+// per shape-bearing link of CFLinks its first shape (the sensor's link is
+// posed through that shape's composed placement), and per contact row its
+// link's index with the torsion rows included (their pure moment belongs to
+// the wrench, though not to the force)
+template <class M> struct FSLinks {
+    static constexpr int NSX = M::NS > 0 ? M::NS : 1, KX = M::NROWS > 0 ? M::NROWS : 1;
+    struct Tab {
+        int first[NSX];
+        int slot[KX];
+    };
+    static constexpr Tab make() {
+        Tab t{};
+        constexpr auto cl = CFLinks<M>::make();
+        for (int c = 0; c < cl.n; ++c)
+            for (int sh = M::NS - 1; sh >= 0; --sh)
+                if (M::shape_link[sh] == cl.link[c]) t.first[c] = sh;
+        for (int j = 0; j < M::NROWS; ++j) t.slot[j] = cl.slot[j] >= 0 ? cl.slot[j] : cl.slot[j - 1];
+        return t;
+    }
+    static constexpr Tab tab = make();
+};
+// a lane's accumulators, 6 floats per sensor it owns
+template <int N> struct FSAcc {
+    float v[N][6] = {};
+};
+template <> struct FSAcc<0> {};
+
 // inverse of the group -> dof map: group of dof d, -1 for a locked dof
 template <class M> struct DofGroup {
     struct Arr {
@@ -1348,6 +1400,29 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
     // pass is over
     constexpr bool DF = PostDF<P>::value;
     [[maybe_unused]] DFAcc<DF ? NR1 : 0> dfa;
+    // force sensor export (NoPostFS): lane sub owns the sensors sub, sub + LPE,
+    // ... and sums their substep wrenches in registers.  A sensor's link is
+    // looked up once: its index among the shape-bearing links (-1: a link
+    // without shapes, which reads zeros) and the first of its shapes
+    constexpr bool FS = PostFS<P>::value && K > 0;
+    constexpr int NFS = FS ? (TG_FS_MAX_SENSORS + LPE - 1) / LPE : 0;
+    [[maybe_unused]] FSAcc<NFS> fsa;
+    [[maybe_unused]] int fsc[NFS > 0 ? NFS : 1], fsh[NFS > 0 ? NFS : 1];
+    if constexpr (FS) {
+#pragma unroll
+        for (int k = 0; k < NFS; ++k) {
+            const int q = sub + k * LPE;
+            const int link = pa.fs && q < pa.fr.n ? pa.fr.c[q < TG_FS_MAX_SENSORS ? q : 0].link : -1;
+            fsc[k] = -1;
+            fsh[k] = 0;
+#pragma unroll
+            for (int i = 0; i < CFLinks<M>::tab.n; ++i) {
+                const bool on = link == CFLinks<M>::tab.link[i];
+                fsc[k] = on ? i : fsc[k];
+                fsh[k] = on ? FSLinks<M>::tab.first[i] : fsh[k];
+            }
+        }
+    }
     for (int sub_i = 0; sub_i < a.substeps; ++sub_i) {
         // Passes 1-3 run with every position/velocity drive implicit and
         // unclamped; if some drive's implicit end-of-substep torque te - K*qdd
@@ -2857,6 +2932,58 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
                     cfa.z[k] += fw.z;
                 }
             }
+            if constexpr (FS) {
+                // the sensor's link's rows summed as above -- the same force,
+                // operation by operation -- and their moments J.w about the
+                // contact group's origin, the torsion row's pure moment among
+                // them; then the shift to the sensor point.  The link is posed
+                // through its first shape's placement in the group frame as
+                // composed for this env (what the rows themselves were built
+                // from, locked and seat-composite groups included): with the
+                // shape's pose in the link (Rso, tso) and in the group (Rx, t),
+                // the point is t + Rx Rso^T (offset - tso) and the link's axes
+                // Rx Rso^T.  CGP holds the pose the substep started from
+#pragma unroll
+                for (int k = 0; k < NFS; ++k) {
+                    const int c = fsc[k];
+                    if (c < 0) continue;
+                    // (bounded() is an assumption, not a clamp: it holds because fsc[k] >= 0 was set above only
+                    // for a lane with sub + k * LPE < pa.fr.n <= TG_FS_MAX_SENSORS -- keep it behind that test)
+                    const int q = bounded(sub + k * LPE, 0, TG_FS_MAX_SENSORS), sh = bounded(fsh[k], 0, FSLinks<M>::NSX);
+                    V3 f = v3(0, 0, 0), m = v3(0, 0, 0);
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        const float l = FSLinks<M>::tab.slot[j] == c ? s(PL::LAM + j) : 0.f;
+                        if (CFLinks<M>::tab.slot[j] >= 0) f = f + l * ldv3(s, PL::ROW + j * 8 + 3);
+                        m = m + l * ldv3(s, PL::ROW + j * 8);
+                    }
+                    int cgi = M::shape_cg[0];
+#pragma unroll
+                    for (int i = 1; i < M::NS; ++i) cgi = sh == i ? M::shape_cg[i] : cgi;
+                    const M3 Rwg = ldm3(s, PL::CGP + 12 * cgi);
+                    M3 Rx, Rso;
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) {
+                        Rx.a[i] = CP(CL::shape(0) + 12 * sh + i);
+                        Rso.a[i] = M::shape_pose[sh][i];
+                    }
+                    const V3 t = v3(CP(CL::shape(0) + 12 * sh + 9), CP(CL::shape(0) + 12 * sh + 10),
+                                    CP(CL::shape(0) + 12 * sh + 11));
+                    const V3 tso = v3(M::shape_pose[sh][9], M::shape_pose[sh][10], M::shape_pose[sh][11]);
+                    const V3 off = v3(pa.fr.c[q].offset[0], pa.fr.c[q].offset[1], pa.fr.c[q].offset[2]);
+                    const M3 Rlg = mul(Rx, transpose(Rso));   // link -> group
+                    const V3 pg = t + mul(Rlg, off - tso);
+                    const V3 rk = mulT(R, mul(Rwg, pg));   // about the group's origin, root frame (as the rows' r)
+                    V3 fw = mul(R, f), nw = mul(R, m - cross(rk, f));
+                    if (pa.fr.space == TG_LOCAL_SPACE) {
+                        const M3 Rl = mul(Rwg, Rlg);
+                        fw = mulT(Rl, fw);
+                        nw = mulT(Rl, nw);
+                    }
+                    fsa.v[k][0] += fw.x; fsa.v[k][1] += fw.y; fsa.v[k][2] += fw.z;
+                    fsa.v[k][3] += nw.x; fsa.v[k][4] += nw.y; fsa.v[k][5] += nw.z;
+                }
+            }
 #ifdef TG_DUMP_ENV
             if (e == tg_dump_env && owner && lead && sub_i == tg_dump_sub) {
                 for (int i = 0; i < K; ++i) {
@@ -3167,7 +3294,7 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
         // one lane owns one group, hence one DOF -- plain stores; the locked
         // DOFs read 0, so the tensor is rewritten in full
         const float inv = a.substeps > 0 ? 1.0f / (float)a.substeps : 0.f;
-        if (owner) {
+        if (owner && (!PostFS<P>::value || pa.df)) {   // (NoPostFS: the DOF tensor may be off)
             float *o = pa.df + (size_t)e * M::ND;
 #pragma unroll
             for (int r = 0; r < NR1; ++r) {
@@ -3179,6 +3306,21 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
             }
             for (int d = sub; d < M::ND; d += LPE)
                 if (M::dof_locked[d]) o[d] = 0.f;
+        }
+    }
+    if constexpr (FS) {
+        // mean wrench over the launch: the impulses' sum / (substeps * h);
+        // zeros when no substep ran, and for a link without shapes.  One lane
+        // owns one sensor: plain stores
+        const float inv = a.substeps > 0 ? 1.0f / ((float)a.substeps * h) : 0.f;
+#pragma unroll
+        for (int k = 0; k < NFS; ++k) {
+            const int q = sub + k * LPE;
+            if (owner && pa.fs && q < pa.fr.n) {
+                float *o = pa.fs + ((size_t)e * pa.fr.n + q) * 6;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) o[i] = inv * fsa.v[k][i];
+            }
         }
     }
     if constexpr (P::on) {

@@ -40,6 +40,13 @@ struct CidArgs {
     float arm2;
 };
 
+// the sensors of tg_set_force_sensor_tensor as the step kernel takes them by value (step_par.h NoPostFS): the
+// frames as registered, their count and the axes of the output (TG_ENV_SPACE / TG_LOCAL_SPACE)
+struct FsFrames {
+    tg_contact_frame c[TG_FS_MAX_SENSORS];
+    int n, space;
+};
+
 // optional Gogoro pre-physics prologue of the compose launch (tg_gogoro_step)
 struct GogoroPre {
     const float *actions;     // [N] (null: none)
@@ -188,12 +195,15 @@ constexpr int JAC_THREADS = 256;   // threads per env of jacobian_kernel
 // kernel) at the most, or the force exports -- cf [N, L, 3], the net contact
 // force of every link that carries a shape (step_par.h NoPostCF), and df
 // [N, D], the DOF forces, written in full (NoPostDF, which exports cf too when
-// it is set).  The exports have no fused-epilogue variant.
+// it is set), and fs [N, S, 6], the force sensor wrenches at the frames fr
+// (NoPostFS, which exports cf and df too when they are set).  The exports
+// have no fused-epilogue variant.
 struct StepPost {
     const WalkPostArgs *walk = nullptr;
     const GogoroPostArgs *gogoro = nullptr;
     const PaperPostArgs *paper = nullptr;
-    float *cf = nullptr, *df = nullptr;
+    float *cf = nullptr, *df = nullptr, *fs = nullptr;
+    FsFrames fr{};
     bool fused() const { return walk || gogoro || paper; }
 };
 // compose + the step kernel that carries post; ev_begin / ev_end (optional)

@@ -77,6 +77,9 @@ struct tg_sim {
     float *cf = nullptr;
     // DOF force tensor [N,D] (tg_set_dof_force_tensor), caller-owned; null: off
     float *df = nullptr;
+    // force sensor tensor [N,S,6] (tg_set_force_sensor_tensor), caller-owned, with its frames; null: off
+    float *fs = nullptr;
+    tg::FsFrames fs_frames{};
     float *env_origin = nullptr;
     uint8_t *dirty = nullptr;
     int *err = nullptr;   // sticky state-error flag set by kernels (tg_sync reports it)
@@ -531,15 +534,17 @@ struct DeviceGuard {
 };
 
 static int simulate_args(tg_sim *s, const tg::StepArgs &a_in, tg::StepPost post = {}) {
-    // the net contact force and DOF force exports have no fused-epilogue
-    // variant: the task steps take their general path (simulates, then the
-    // post-physics launch)
-    if ((s->cf || s->df) && post.fused()) {
+    // the net contact force, DOF force and force sensor exports have no
+    // fused-epilogue variant: the task steps take their general path
+    // (simulates, then the post-physics launch)
+    if ((s->cf || s->df || s->fs) && post.fused()) {
         s->stats[5]++;
         return 1;
     }
     post.cf = s->cf;
     post.df = s->df;
+    post.fs = s->fs;
+    post.fr = s->fs_frames;
     DeviceGuard dg(s->device);
     tg::StepArgs a = a_in;
     // the compose launch: every dirty env (host-side changes possible), the
@@ -936,6 +941,46 @@ int tg_set_dof_force_tensor(tg_sim *s, float *out) {
     // until the first simulate the tensor reads 0)
     HIPCHK(hipMemsetAsync(out, 0, (size_t)s->N * s->D * sizeof(float), s->stream));
     s->df = out;
+    return TG_OK;
+}
+
+int tg_set_force_sensor_tensor(tg_sim *s, const tg_contact_frame *sensors, int32_t num_sensors, int32_t space,
+                               float *out) {
+    const char *fn = "tg_set_force_sensor_tensor";
+    if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
+    if (num_sensors < 0 || num_sensors > TG_FS_MAX_SENSORS)
+        return fail(TG_ERR_ARG, "%s: num_sensors %d outside 0..%d", fn, num_sensors, TG_FS_MAX_SENSORS);
+    if (num_sensors > 0 && !sensors) return fail(TG_ERR_ARG, "%s: null sensors", fn);
+    if (space != TG_ENV_SPACE && space != TG_LOCAL_SPACE)
+        return fail(TG_ERR_ARG, "%s: space %d is neither TG_ENV_SPACE nor TG_LOCAL_SPACE", fn, space);
+    if (out && num_sensors == 0) return fail(TG_ERR_ARG, "%s: an output tensor with num_sensors 0", fn);
+    tg::FsFrames fr{};
+    for (int k = 0; k < num_sensors; ++k) {
+        const int l = sensors[k].link;
+        if (l < 0 || l >= s->L) return fail(TG_ERR_ARG, "%s: sensor %d: link %d outside [0, %d)", fn, k, l, s->L);
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(sensors[k].offset[i]))
+                return fail(TG_ERR_ARG, "%s: sensor %d: offset[%d] is not finite", fn, k, i);
+        fr.c[k] = sensors[k];
+    }
+    if (!out || num_sensors == 0) {
+        s->fs = nullptr;
+        s->fs_frames = tg::FsFrames{};
+        return TG_OK;
+    }
+    if (tg::jit_has(s->hash))
+        return fail(TG_ERR_MODEL,
+                    "%s: the force sensor export exists for compiled-in models only, not for a model compiled at "
+                    "run time (tg_model_jit)", fn);
+    fr.n = num_sensors;
+    fr.space = space;
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    // sensors on links without a shape, and every sensor of a model without
+    // contact rows, are never written by the step kernel: they read 0
+    HIPCHK(hipMemsetAsync(out, 0, (size_t)s->N * num_sensors * 6 * sizeof(float), s->stream));
+    s->fs = out;
+    s->fs_frames = fr;
     return TG_OK;
 }
 

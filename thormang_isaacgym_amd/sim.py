@@ -171,6 +171,9 @@ class Sim:
         check(lib().tg_sim_create(C.byref(self.desc.desc), C.byref(params), N, self.device.index or 0, C.byref(h)),
               "tg_sim_create")
         self._h = h
+        # the force sensor tensor and what it was registered with (acquire_force_sensor_tensor); None: off
+        self.force_sensor = None
+        self._force_sensor_key = None
         self.stream = torch.cuda.current_stream(self.device)
         check(lib().tg_set_stream(self._h, C.c_void_p(self.stream.cuda_stream)), "tg_set_stream")
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -359,6 +362,44 @@ class Sim:
     def refresh_dof_force_tensor(self):
         """gym.refresh_dof_force_tensor (tasks/MA_OP3.py:96): the tensor is
         written by simulate itself, nothing to do."""
+
+    def acquire_force_sensor_tensor(self, sensors, space: str = "env") -> torch.Tensor:
+        """gym.acquire_force_sensor_tensor (tasks/humanoid.py:167), with the
+        sensors given here instead of through create_asset_force_sensor:
+        ``sensors`` is a list of ``contact_frame(link, offset)`` (at most
+        ``abi.TG_FS_MAX_SENSORS``; link names or indices stand for a frame at
+        the link origin).  Returns the live [N, S, 6] tensor: per sensor the
+        ground's force on the sensor's link and its moment about the sensor
+        point (newtons, newton metres), averaged over the last simulate's
+        substeps and written by every simulate from now on (tgsim.h
+        tg_set_force_sensor_tensor).  ``space``: "env" for world axes, the
+        convention of ``ContactDynamics.wrench``, or "local" for the link's own
+        axes.  It is the ground reaction alone -- no gravity or inertial part,
+        nothing from the links further down the chain -- and 0 for a link
+        without collision shapes.  The same sensors and space again return the
+        same tensor; other ones re-register and return a new tensor.  An empty
+        ``sensors`` list turns the tensor off (``force_sensor`` is None again,
+        the fused task steps are back) and returns an empty [N, 0, 6] tensor.
+        Compiled-in models only; the task steps run unfused while it is on."""
+        if space not in ("env", "local"):
+            raise ValueError(f"space {space!r} is neither 'env' nor 'local'")
+        sensors = [c if isinstance(c, abi.tg_contact_frame) else self.contact_frame(c) for c in sensors]
+        key = (space, tuple((int(c.link), tuple(float(v) for v in c.offset)) for c in sensors))
+        if self.force_sensor is not None and self._force_sensor_key == key:
+            return self.force_sensor
+        S = len(sensors)
+        t = torch.zeros(self.num_envs, S, 6, dtype=torch.float32, device=self.device)
+        frames = (abi.tg_contact_frame * max(S, 1))(*sensors)
+        check(lib().tg_set_force_sensor_tensor(self._h, frames, S, abi.TG_LOCAL_SPACE if space == "local"
+                                               else abi.TG_ENV_SPACE, _ptr(t) if S else None),
+              "acquire_force_sensor_tensor")
+        self.force_sensor = t if S else None
+        self._force_sensor_key = key if S else None
+        return t
+
+    def refresh_force_sensor_tensor(self):
+        """gym.refresh_force_sensor_tensor (tasks/humanoid.py:243): the tensor
+        is written by simulate itself, nothing to do."""
 
     def acquire_jacobian_tensor(self) -> torch.Tensor:
         """gym.acquire_jacobian_tensor (tasks/gogoro/gogoro.py:108-114): the link

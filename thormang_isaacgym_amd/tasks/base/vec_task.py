@@ -252,6 +252,15 @@ class VecTask(Env):
         """gym.refresh_dof_force_tensor (tasks/MA_OP3.py:96)."""
         self.sim.refresh_dof_force_tensor()
 
+    def acquire_force_sensor_tensor(self, sensors, space: str = "env") -> torch.Tensor:
+        """gym.acquire_force_sensor_tensor (tasks/humanoid.py:167): the sim's
+        live [N, S, 6] tensor of ground-reaction wrenches at ``sensors``."""
+        return self.sim.acquire_force_sensor_tensor(sensors, space)
+
+    def refresh_force_sensor_tensor(self):
+        """gym.refresh_force_sensor_tensor (tasks/humanoid.py:243)."""
+        self.sim.refresh_force_sensor_tensor()
+
     def acquire_jacobian_tensor(self) -> torch.Tensor:
         """gym.acquire_jacobian_tensor (tasks/gogoro/gogoro.py:108-114): the sim's
         [N, L, 6, D+6] link Jacobians ([N, L-1, 6, D] with a fixed base; Sim)."""

@@ -36,6 +36,15 @@ inertia (tgsim.h tg_centroidal) of the state the step returns with, one extra
 kernel launch per step -- for CoM height, capture-point or angular-momentum
 terms a user adds.  Observation, reward and reset do not read it, and the step
 itself is unchanged.
+
+``env.enableFootForceSensors: true`` (optional, default false) registers one
+force sensor per foot (tgsim.h tg_set_force_sensor_tensor) at the centre of the
+sole -- the centre of the bottom face of the foot's collision box, taken from
+the model's shape -- in the foot link's own axes: ``force_sensors`` [N,2,6] and
+``extras["feet_force_sensor"]`` after every step, the ground's force on each
+foot and its moment about the sole centre, for centre-of-pressure, ZMP or
+torsional-load terms a user adds.  Observation, reward and reset do not read
+them.  The step runs unfused as above.
 """
 from __future__ import annotations
 
@@ -107,6 +116,14 @@ class ThormangWalk(VecTask):
         # (tasks/MA_OP3.py:91,96,275); observation, reward and reset do not use them
         if bool(env.get("enableDofForceSensors", False)):
             self.dof_forces = self.acquire_dof_force_tensor()
+            self._contact_extras()
+        # env.enableFootForceSensors: the ground's wrench on each foot at the centre of its sole, foot axes
+        # (tasks/humanoid.py:80,167-168,243); observation, reward and reset do not use them
+        self.force_sensors = None
+        if bool(env.get("enableFootForceSensors", False)):
+            self.force_sensors = self.acquire_force_sensor_tensor(
+                [self.sim.contact_frame(l, walk_sole_centre(self.model, l)) for l in walk_feet_indices(self.model)],
+                space="local")
             self._contact_extras()
         # env.enableCentroidalState: com, com velocity, angular momentum, mass and centroidal inertia of the state a
         # step returns with (tg_centroidal); observation, reward and reset do not use them
@@ -194,6 +211,9 @@ class ThormangWalk(VecTask):
         # extras["dof_force"] [N, D]: the DOF force tensor (env.enableDofForceSensors)
         if self.dof_forces is not None:
             self.extras["dof_force"] = self.dof_forces.to(self.rl_device)
+        # extras["feet_force_sensor"] [N, 2, 6]: the feet's force sensors (env.enableFootForceSensors)
+        if getattr(self, "force_sensors", None) is not None:
+            self.extras["feet_force_sensor"] = self.force_sensors.to(self.rl_device)
         # extras["centroidal"] [N, 16]: the centroidal state (env.enableCentroidalState)
         if getattr(self, "centroidal_state", None) is not None:
             self.extras["centroidal"] = self.centroidal(out=self.centroidal_state).state.to(self.rl_device)
@@ -240,6 +260,16 @@ def walk_feet_indices(m) -> list:
     carry a collision shape, as indices into ``m.links``."""
     from ..sim import contact_link_indices
     return [i for i in contact_link_indices(m) if "foot" in m.links[i].name]
+
+
+def walk_sole_centre(m, link: int):
+    """The centre of the sole of foot ``link`` in the link's frame: the centre
+    of the bottom face (the one facing the link's -z) of its collision box."""
+    s = next(s for s in m.shapes if m.link_index(s.link) == link and s.kind == "box")
+    rot = np.asarray(s.rot, np.float64).reshape(3, 3)
+    k = int(np.argmax(np.abs(rot[2])))          # the box axis along the link's z
+    down = -np.sign(rot[2, k]) * rot[:, k]      # its direction towards -z
+    return [float(v) for v in np.asarray(s.pos, np.float64) + float(s.params[k]) * down]
 
 
 def walk_asset_options(cfg) -> dict:
