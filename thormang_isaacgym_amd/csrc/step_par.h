@@ -1187,6 +1187,39 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
         if (1 + sub < M::NG) vlim1 = PR(TG_PROP_VELOCITY, bounded(gi[(1 + sub) * GIW + GI_DOF], 0, 1 << 16));
         load_inertia(cin1);
     }
+    // trees of several rounds (the humanoids: 34 groups on 16 lanes): the same
+    // inputs of every round of the lane, for the same reason -- issued here,
+    // ahead of the first substep's pass 1; pass 2a of every substep and of the
+    // clamp rerun, and the integration, read them from registers (clamped
+    // group index: the loads are unconditional).  With pm_in_step the position
+    // target is formed from the actions, so no load here waits on the
+    // pre-physics' stores above.
+    // Not where the contact rows already fill the 512-entry register file
+    // (the whole-body model, 42 rows: holding the values there spills,
+    // 0 / 40 / 80 -> 48 / 144 / 200 B of scratch per lane): those kernels
+    // keep the loads in pass 2a and at the top of the substep.
+    // (load_drv per round, as pass 2a called it: other arrangements of these
+    // loads -- all rounds' loads ahead of the first target, the target formed
+    // in pass 2a -- made the compiler contract pass 2a's kp * (..) + kd * (..)
+    // the other way round, which rounds differently)
+    constexpr bool DRVL = NR1 > 1 && PL::K <= 2 * LPE;
+    float cdl[DRVL ? NR1 : 1][10], vliml[DRVL ? NR1 : 1];
+    if constexpr (DRVL) {
+#pragma unroll
+        for (int r = 0; r < NR1; ++r) {
+            const int gc = min(max(sub + r * LPE, 1), M::NG - 1);
+            load_drv(bounded(gi[gc * GIW + GI_DOF], 0, 1 << 16), cdl[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < NR1; ++r) {
+            const int g = 1 + sub + r * LPE;
+            vliml[r] = g < M::NG ? PR(TG_PROP_VELOCITY, bounded(gi[g * GIW + GI_DOF], 0, 1 << 16)) : 0.f;
+        }
+    }
+    // and the composite inertia rows of the lane's groups (36 values), which
+    // every substep reloaded a pass ahead of their use
+    float cinl[DRVL ? NR1 : 1][12];
+    if constexpr (DRVL) load_inertia(cinl);
     // one-round trees: every schedule step's joint placement too (constant
     // over the launch: the epilogue's in-place seat moves come after the last
     // substep), so pass 1a waits for them once per launch, not once per substep
@@ -1438,10 +1471,14 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
         wn = 0;
         auto wood_update = [&]() { return wood_update_impl(rootf, a0); };
         // velocity limits of the lane's groups (used by the integration at the
-        // end of the substep), issued now so their latency is hidden
+        // end of the substep): loaded once per launch (below the prologue),
+        // or issued now so their latency is hidden
         float vlim[(M::NG + LPE - 1) / LPE];
         if constexpr (NR1 == 1) {
             vlim[0] = vlim1;
+        } else if constexpr (DRVL) {
+#pragma unroll
+            for (int r = 0; r < NR1; ++r) vlim[r] = vliml[r];
         } else {
 #pragma unroll
         for (int r = 0; r < (M::NG + LPE - 1) / LPE; ++r) {
@@ -1479,6 +1516,11 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
         if constexpr (NR1 == 1) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) cin[0][k] = cin1[0][k];
+        } else if constexpr (DRVL) {
+#pragma unroll
+            for (int r = 0; r < NR1; ++r)
+#pragma unroll
+                for (int k = 0; k < 12; ++k) cin[r][k] = cinl[r][k];
         } else {
             load_inertia(cin);
         }
@@ -1672,15 +1714,19 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
         // pass 3 reads too; F_DINV: c0, F_UU: tau, F_QDS: limit torque per D0, F_C1: 1 +
         // limit gain per D0)
         if constexpr (NR1 > 1) {
-        // Every round's drive inputs are loaded first (clamped group index: the
-        // loads are unconditional) and consumed by branch-free arithmetic with
-        // only the stores predicated, so the compiler cannot sink a load into a
-        // conditional block that uses it: the rounds share one memory latency.
-        float cdr[NR1][10];
+        // Every round's drive inputs are in registers, loaded once per launch
+        // (DRVL, below the prologue), or loaded here first (clamped group
+        // index: the loads are unconditional), and consumed by branch-free
+        // arithmetic with only the stores predicated, so the compiler cannot
+        // sink a load into a conditional block that uses it: the rounds share
+        // one memory latency.
+        float cdr[DRVL ? 1 : NR1][10];
+        if constexpr (!DRVL) {
 #pragma unroll
         for (int r = 0; r < NR1; ++r) {
             const int gc = min(max(sub + r * LPE, 1), M::NG - 1);
             load_drv(bounded(gi[gc * GIW + GI_DOF], 0, 1 << 16), cdr[r]);
+        }
         }
 #pragma unroll
         for (int r = 0; r < NR1; ++r) {
@@ -1688,7 +1734,9 @@ __global__ __launch_bounds__(EPB * M::LPE) void step_par_kernel(StepArgs a, type
             const bool valid = g0 > 0 && g0 < M::NG;
             const int g = min(max(g0, 1), M::NG - 1);
             const int o = g * GF;
-            const float *cd = cdr[r];
+            const float *cd;
+            if constexpr (DRVL) cd = cdl[r];
+            else cd = cdr[r];
             const float q = s(o + F_Q), qd = s(o + F_QD), qdd0 = s(o + F_UU);
             const int mode = (int)rintf(cd[1]);
             const float kp = cd[2], kd = cd[3];
