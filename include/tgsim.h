@@ -83,6 +83,11 @@
  *                            distributed over up to four contact links by least
  *                            squares, the joint torques that are left and the
  *                            predicted contact wrenches
+ *   tg_height_scan           measured_heights: get_heights on init_height_points
+ *                            with quat_apply_yaw, and the clipped, scaled height
+ *                            observation (tasks/anymal_terrain.py:501-536,
+ *                            :301-302), about any link frames, on the surface the
+ *                            contacts feel or by the reference's cell rule
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -749,6 +754,82 @@ int tg_contact_inverse_dynamics(tg_sim *sim, const tg_contact_frame *contacts /*
 #define TG_FS_MAX_SENSORS 8
 int tg_set_force_sensor_tensor(tg_sim *sim, const tg_contact_frame *sensors /* HOST */, int32_t num_sensors,
                                int32_t space /* TG_ENV_SPACE | TG_LOCAL_SPACE */, float *out /* [N, S, 6] device */);
+/* The ground under the robot in one kernel: terrain heights, and optionally
+ * the surface normals, at a pattern of points about up to TG_SCAN_MAX_FRAMES
+ * link frames -- the height scan around the base that terrain locomotion
+ * observes (measured_heights: get_heights with init_height_points,
+ * tasks/anymal_terrain.py:501-536, entering the observation at :301-302), and,
+ * with the feet as frames, the swing-foot clearance and the slope under a
+ * sole.  On demand, stream-ordered, from the current root and dof state and
+ * the heightfield the sim holds at the time of the call (tg_set_heightfield; a
+ * later change, removal with rows = 0 included, is seen by the next call);
+ * nothing of the sim is written and nothing is kept on the host between calls.
+ * A NULL output is not touched; every element of every non-NULL output is
+ * written.
+ *
+ * Frame f is the point
+ *   p_f = o_l + R_l offset_f
+ * on link l_f, the convention of tg_contact_frame, tg_set_force_sensor_tensor
+ * and tg_ik_chain.offset, o_l and R_l those of tg_rigid_body_states (world
+ * coordinates, the ones the contacts' ground takes); a link may appear in
+ * several frames.  points [P, 2] is one pattern for every env and frame.  The
+ * sample of pattern point (a, b) = points[k] is at the world position
+ *   (x, y) = (p_f.x, p_f.y) + d.xy
+ *   TG_SCAN_WORLD   d = (a, b, 0)
+ *   TG_SCAN_LINK    d = R_l (a, b, 0): laid out in the link's own axes, then
+ *                   dropped vertically
+ *   TG_SCAN_YAW     d = Rz(psi) (a, b, 0), Rz(psi) the reference's
+ *                   quat_apply_yaw: the link's quaternion with x and y zeroed,
+ *                   normalised.  (cos psi, sin psi) is (R00 + R11, R10 - R01)
+ *                   normalised; the identity when both are 0
+ * and h, n there are
+ *   TG_SCAN_SURFACE the surface the contacts feel, by the very function the
+ *                   step kernel's contact rows call (ground_at): the triangle
+ *                   rule of tg_set_heightfield or the z = 0 plane, whichever is
+ *                   higher, the plane outside the grid, n the unit normal of
+ *                   the triangle (e_z on the plane).  Without a heightfield
+ *                   h = 0 and n = e_z
+ *   TG_SCAN_CELL    the reference's rule (anymal_terrain.py:524-536):
+ *                   u = (x - ox) / hs, i = clamp(trunc(u), 0, rows - 2), j
+ *                   likewise from y, h = vs min(hf[i][j], hf[i+1][j+1]).  No
+ *                   plane; a point off the grid reads the border cell.
+ *                   Without a heightfield h = 0.  There is no normal: normals
+ *                   must be NULL
+ *
+ * heights[e, f, k] = h with params.relative == 0; otherwise
+ *   heights[e, f, k] = clamp(p_f.z - bias - h, lo, hi) * scale
+ * which is line 302 of the reference in the same launch (bias 0.5, clip +-1,
+ * height_meas_scale) and, at a foot, its clearance.  normals[e, f, k] = n.
+ * bias, lo, hi and scale are not read with relative == 0.
+ *
+ * The link poses are formed relative to the root link's origin and the root
+ * position is added last, as in tg_centroidal; p_f agrees with
+ * tg_rigid_body_states to rounding.  Envs do not interact: an env's results
+ * do not depend on the other envs' states.
+ *
+ * TG_ERR_ARG (message "tg_height_scan: ...") for a null sim, frames, points or
+ * params, num_frames outside 1..TG_SCAN_MAX_FRAMES, num_points outside
+ * 1..TG_SCAN_MAX_POINTS, a link outside [0, L), a non-finite offset, surface
+ * outside {0, 1}, align outside {0, 1, 2}, relative != 0 with a non-finite
+ * bias or scale or without lo <= hi, normals together with TG_SCAN_CELL, and
+ * heights and normals both NULL.  A rejected call launches nothing.  Every
+ * model, run-time (tg_model_jit) ones included. */
+#define TG_SCAN_MAX_FRAMES 8
+#define TG_SCAN_MAX_POINTS 1024
+#define TG_SCAN_SURFACE 0   /* the trimesh surface the contacts feel (ground_at) */
+#define TG_SCAN_CELL    1   /* the reference's rule, anymal_terrain.py:524-536   */
+#define TG_SCAN_YAW   0     /* pattern turned by the frame link's heading        */
+#define TG_SCAN_WORLD 1     /* pattern in world axes                             */
+#define TG_SCAN_LINK  2     /* pattern in the link's own axes, then dropped vertically */
+typedef struct tg_scan_params {   /* HOST, read during the call */
+    int32_t surface, align, relative;
+    float bias, lo, hi, scale;    /* used when relative != 0 */
+} tg_scan_params;                 /* 28 bytes */
+int tg_height_scan(tg_sim *sim, const tg_contact_frame *frames /* HOST */, int32_t num_frames,
+                   const float *points /* [P, 2] device */, int32_t num_points,
+                   const tg_scan_params *params /* HOST */,
+                   float *heights /* [N, F, P] device or NULL */,
+                   float *normals /* [N, F, P, 3] device or NULL */);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

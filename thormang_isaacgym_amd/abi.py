@@ -84,6 +84,19 @@ assert C.sizeof(tg_contact_frame) == 16
 TG_FS_MAX_SENSORS = 8                   # sensors of tg_set_force_sensor_tensor (they are tg_contact_frames too)
 TG_ENV_SPACE, TG_LOCAL_SPACE = 0, 1     # axes of per-link vectors (tgsim.h)
 
+TG_SCAN_MAX_FRAMES, TG_SCAN_MAX_POINTS = 8, 1024   # frames (tg_contact_frames too) and pattern points of tg_height_scan
+TG_SCAN_SURFACE, TG_SCAN_CELL = 0, 1               # the surface the contacts feel / the reference's cell rule
+TG_SCAN_YAW, TG_SCAN_WORLD, TG_SCAN_LINK = 0, 1, 2  # how the pattern is turned about a frame
+
+
+class tg_scan_params(C.Structure):
+    """The rule, the alignment and the relative map of tg_height_scan (tgsim.h)."""
+    _fields_ = [("surface", C.c_int32), ("align", C.c_int32), ("relative", C.c_int32),
+                ("bias", C.c_float), ("lo", C.c_float), ("hi", C.c_float), ("scale", C.c_float)]
+
+
+assert C.sizeof(tg_scan_params) == 28
+
 
 class tg_osc_gains(C.Structure):
     """The gains of tg_osc (tgsim.h): task-space kp / kd, null-space kp_null / kd_null, the damping lambda."""

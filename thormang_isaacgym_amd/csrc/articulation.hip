@@ -205,6 +205,15 @@ int launch_centroidal(uint64_t hash, const float *root, const float *dof, const 
     }) ? rc : jit_launch_centroidal(hash, root, dof, mass_scale, n, state, matrix, bias, stream);
 }
 
+int launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
+                       const ScanArgs &sa, float *heights, float *normals, hipStream_t stream) {
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(height_scan_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, points, n, sa, heights,
+                 normals);
+    }) ? rc : jit_launch_height_scan(hash, root, dof, points, n, sa, heights, normals, stream);
+}
+
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {

@@ -11,6 +11,7 @@
 
 #include "../../include/tgsim.h"
 #include "gogoro_math.h"
+#include "ground.h"
 #include "tg_math.h"
 #include "tg_kernels.h"
 
@@ -2085,6 +2086,99 @@ __global__ __launch_bounds__(64) void centroidal_kernel(const float *root, const
         }
         o[col] = ff.x; o[C + col] = ff.y; o[2 * C + col] = ff.z;
         o[3 * C + col] = nn.x; o[4 * C + col] = nn.y; o[5 * C + col] = nn.z;
+    }
+}
+
+// Height scan (tgsim.h tg_height_scan): the ground height, and optionally its
+// normal, under a pattern of P points about F link frames, heights [N, F, P]
+// and normals [N, F, P, 3].  One wavefront per env:
+//   lanes        forward kinematics (fk_root_relative)
+//   lane = frame the frame point p_f = o_l + R_l offset_f, relative to the root
+//                origin with the root position added last, and the 2 x 2 map of
+//                the pattern into world x, y -- the identity, the link's own
+//                R[0:2, 0:2], or the heading Rz(psi) with (cos psi, sin psi) =
+//                (R00 + R11, R10 - R01) normalised -- eight floats per frame
+//                in LDS
+//   lanes        stride over the F P samples in output order, so that a wave
+//                stores 256 contiguous bytes of heights per pass: the sample's
+//                x, y, then ground_at (ground.h, the function of the step
+//                kernel's contact rows) or the reference's cell rule -- four or
+//                two reads of a table that stays in L2 -- and the relative map
+// Which outputs are null, the rule and the alignment are uniform over the
+// launch.  Every index into the table is clamped to the grid (ground_at returns
+// before it forms one for a point outside, NaN included).  Wave-level syncs
+// only, plain stores, no atomics.
+template <class M>
+__global__ __launch_bounds__(64) void height_scan_kernel(const float *root, const float *dof, const float *points,
+                                                         int n, ScanArgs a, float *heights, float *normals) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    __shared__ float T[M::NL][12], A[M::NL][3];
+    __shared__ __align__(16) float FR[TG_SCAN_MAX_FRAMES][8];   // p_f (3), a pad, the map m00 m01 m10 m11
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e;
+    fk_root_relative<M>(r, dof + 2 * (size_t)e * M::ND, lane, T, A);
+    if (lane < a.F) {
+        const int l = a.f[lane].link;
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const V3 p = v3(T[l][9], T[l][10], T[l][11]) +
+                     mul(R, v3(a.f[lane].offset[0], a.f[lane].offset[1], a.f[lane].offset[2]));
+        float m00 = 1.f, m01 = 0.f, m10 = 0.f, m11 = 1.f;
+        if (a.p.align == TG_SCAN_LINK) {
+            m00 = R.a[0]; m01 = R.a[1]; m10 = R.a[3]; m11 = R.a[4];
+        } else if (a.p.align == TG_SCAN_YAW) {
+            const float c = R.a[0] + R.a[4], s = R.a[3] - R.a[1], d2 = c * c + s * s;
+            if (d2 > 0.f) {
+                const float in = rsqrtf(d2);
+                m00 = c * in; m01 = -(s * in); m10 = s * in; m11 = c * in;
+            }
+        }
+        // the root position is added last: the relative frame point does not depend on where the env sits
+        *reinterpret_cast<float4 *>(FR[lane]) = make_float4(r[0] + p.x, r[1] + p.y, r[2] + p.z, 0.f);
+        *reinterpret_cast<float4 *>(FR[lane] + 4) = make_float4(m00, m01, m10, m11);
+    }
+    wsync();
+    const int P = a.P, S = a.F * P;
+    const size_t base = (size_t)e * S;
+    const float2 *pts = reinterpret_cast<const float2 *>(points);
+    for (int s = lane; s < S; s += 64) {
+        const int f = s / P, k = s - f * P;
+        const float2 ab = pts[k];
+        const float4 pf = *reinterpret_cast<const float4 *>(FR[f]);
+        const float4 mp = *reinterpret_cast<const float4 *>(FR[f] + 4);
+        const float x = pf.x + (mp.x * ab.x + mp.y * ab.y), y = pf.y + (mp.z * ab.x + mp.w * ab.y);
+        float h = 0.f;
+        V3 nn = v3(0.f, 0.f, 1.f);
+        if (a.hf) {
+            if (a.p.surface == TG_SCAN_SURFACE) {
+                bool on;
+                h = ground_at(a, x, y, nn, on);
+            } else {
+                // clamp(trunc(u), 0, rows - 2): clamped as a float first, so that the conversion sees a value on the
+                // grid, and again as an integer, so that the index is on the grid whatever the conversion made of a NaN
+                const float u = (x - a.hf_ox) / a.hf_hs, v = (y - a.hf_oy) / a.hf_hs;
+                const int i = min(max((int)fminf(fmaxf(u, 0.f), (float)(a.hf_rows - 2)), 0), a.hf_rows - 2);
+                const int j = min(max((int)fminf(fmaxf(v, 0.f), (float)(a.hf_cols - 2)), 0), a.hf_cols - 2);
+                const float *c0 = a.hf + (size_t)i * a.hf_cols + j;
+                h = a.hf_vs * fminf(c0[0], c0[a.hf_cols + 1]);
+            }
+        }
+        if (heights) {
+            if (a.p.relative) h = fminf(fmaxf(pf.z - a.p.bias - h, a.p.lo), a.p.hi) * a.p.scale;
+            heights[base + s] = h;
+        }
+        if (normals) {
+            float *o = normals + (base + s) * 3;
+            o[0] = nn.x; o[1] = nn.y; o[2] = nn.z;
+        }
     }
 }
 

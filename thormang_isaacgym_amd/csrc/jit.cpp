@@ -34,7 +34,8 @@
 namespace tg {
 namespace {
 
-enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, K_ID, K_CENTROIDAL, K_CID, NK };
+enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, K_ID, K_CENTROIDAL, K_CID, K_SCAN,
+       NK };
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, false, tg::NoPost>",
@@ -48,6 +49,7 @@ const char *const KERNEL_EXPR[NK] = {
     "tg::inverse_dynamics_kernel<TgJitModel>",
     "tg::centroidal_kernel<TgJitModel>",
     "tg::contact_inverse_dynamics_kernel<TgJitModel>",
+    "tg::height_scan_kernel<TgJitModel>",
 };
 // the per-model launch figures the host needs, read back from the module
 // (tgjit_meta, same order)
@@ -69,7 +71,7 @@ std::map<uint64_t, JitCode> g_code;                            // by model hash
 std::map<std::pair<uint64_t, int>, JitLoaded> g_loaded;       // by (hash, device)
 
 const char *const HEADERS[] = {"articulation_kernels.h", "step_par.h", "tg_math.h", "gogoro_math.h", "paper_math.h",
-                               "tg_kernels.h",
+                               "tg_kernels.h", "ground.h",
                                "../../include/tgsim.h", "../../include/tg_gogoro.h",
                                "../../include/tg_gogoro_paper.h", "../../include/tg_walk.h"};
 
@@ -156,7 +158,7 @@ int compile(const std::string &src, const std::string &incdir, JitCode &out, std
     return 0;
 }
 
-// cache file: "TGJIT7\n", one lowered name per line, then the code object
+// cache file: "TGJIT8\n", one lowered name per line, then the code object
 bool cache_load(const std::string &path, JitCode &out) {
     std::string s;
     if (!read_file(path, s)) return false;
@@ -169,7 +171,7 @@ bool cache_load(const std::string &path, JitCode &out) {
         return true;
     };
     std::string magic;
-    if (!line(magic) || magic != "TGJIT7") return false;
+    if (!line(magic) || magic != "TGJIT8") return false;
     for (int k = 0; k < NK; ++k)
         if (!line(out.names[k]) || out.names[k].empty()) return false;
     if (pos >= s.size()) return false;
@@ -182,7 +184,7 @@ void cache_store(const std::string &path, const JitCode &c) {
     {
         std::ofstream f(tmp, std::ios::binary);
         if (!f) return;
-        f << "TGJIT7\n";
+        f << "TGJIT8\n";
         for (int k = 0; k < NK; ++k) f << c.names[k] << "\n";
         f.write(c.code.data(), (std::streamsize)c.code.size());
         if (!f) return;
@@ -379,6 +381,15 @@ int jit_launch_centroidal(uint64_t hash, const float *root, const float *dof, co
     if (!L) return TG_ERR_MODEL;
     void *args[] = {&root, &dof, &mass_scale, &n, &state, &matrix, &bias};
     return launch(L->f[K_CENTROIDAL], (unsigned)n, 64, 0, stream, args);
+}
+
+int jit_launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
+                           const ScanArgs &sa, float *heights, float *normals, hipStream_t stream) {
+    JitLoaded *L = find(hash);
+    if (!L) return TG_ERR_MODEL;
+    ScanArgs aa = sa;
+    void *args[] = {&root, &dof, &points, &n, &aa, &heights, &normals};
+    return launch(L->f[K_SCAN], (unsigned)n, 64, 0, stream, args);
 }
 
 }  // namespace tg

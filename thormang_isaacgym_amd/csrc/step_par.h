@@ -40,6 +40,8 @@
 // root LDL factor) are computed redundantly in all lanes of the env.
 #pragma once
 
+#include "ground.h"
+
 namespace tg {
 
 #ifdef TG_SECTION_PROF
@@ -526,32 +528,8 @@ __device__ __forceinline__ float inv_diag(float w) { return w > TG_W_DEAD ? 1.0f
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
     } while (0)
 
-// Ground surface under world (x, y): the heightfield trimesh of
-// tg_set_heightfield (vertex (i,j) at (ox + i hs, oy + j hs, vs h[i][j]);
-// cell triangles (i,j)-(i+1,j+1)-(i,j+1) for fv >= fu and
-// (i,j)-(i+1,j)-(i+1,j+1) for fu >= fv) or the z = 0 plane, whichever is
-// higher.  Returns the height, the unit normal in n and whether the terrain
-// is the surface.  oracle/physics_ref.c ground_at is the same function.
-__device__ __forceinline__ float ground_at(const StepArgs &a, float x, float y, V3 &n, bool &on_hf) {
-    n = v3(0, 0, 1);
-    on_hf = false;
-    const float u = (x - a.hf_ox) / a.hf_hs, v = (y - a.hf_oy) / a.hf_hs;
-    if (!(u >= 0.f && v >= 0.f && u <= (float)(a.hf_rows - 1) && v <= (float)(a.hf_cols - 1))) return 0.f;
-    const int i = min((int)u, a.hf_rows - 2), j = min((int)v, a.hf_cols - 2);
-    const float fu = u - (float)i, fv = v - (float)j;
-    const float *r0 = a.hf + (size_t)i * a.hf_cols + j, *r1 = r0 + a.hf_cols;
-    const float h00 = a.hf_vs * r0[0], h01 = a.hf_vs * r0[1], h10 = a.hf_vs * r1[0], h11 = a.hf_vs * r1[1];
-    float H, gx, gy;
-    if (fu >= fv) { gx = h10 - h00; gy = h11 - h10; H = h00 + fu * gx + fv * gy; }
-    else          { gx = h11 - h01; gy = h01 - h00; H = h00 + fu * gx + fv * gy; }
-    if (!(H > 0.f)) return 0.f;
-    gx /= a.hf_hs;
-    gy /= a.hf_hs;
-    const float inv = 1.f / sqrtf(gx * gx + gy * gy + 1.f);
-    n = v3(-gx * inv, -gy * inv, inv);
-    on_hf = true;
-    return H;
-}
+// (the ground surface under a contact point, ground_at: ground.h, shared with
+// the height scan)
 
 // Optional fused epilogue P: a task's post-physics step run by the step
 // kernel on the final state (still in registers / LDS) instead of a separate

@@ -40,6 +40,18 @@ struct CidArgs {
     float arm2;
 };
 
+// what a tg_height_scan call hands height_scan_kernel by value: the frames, the counts, tg_scan_params and the
+// sim's heightfield at the time of the call under the member names of StepArgs, which ground_at (ground.h) reads
+// (hf null: no terrain)
+struct ScanArgs {
+    tg_contact_frame f[TG_SCAN_MAX_FRAMES];
+    int F, P;
+    tg_scan_params p;
+    const float *hf;
+    int hf_rows, hf_cols;
+    float hf_hs, hf_vs, hf_ox, hf_oy;
+};
+
 // the sensors of tg_set_force_sensor_tensor as the step kernel takes them by value (step_par.h NoPostFS): the
 // frames as registered, their count and the axes of the output (TG_ENV_SPACE / TG_LOCAL_SPACE)
 struct FsFrames {
@@ -243,6 +255,10 @@ int launch_contact_inverse_dynamics(uint64_t hash, const float *root, const floa
 // (centroidal_kernel; tgsim.h tg_centroidal)
 int launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n, float *state,
                       float *matrix, float *bias, hipStream_t stream);
+// terrain heights [N, F, P] and normals [N, F, P, 3], each optional, under the pattern points [P, 2] about F link
+// frames (height_scan_kernel; tgsim.h tg_height_scan)
+int launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
+                       const ScanArgs &sa, float *heights, float *normals, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
@@ -288,6 +304,8 @@ int jit_launch_contact_inverse_dynamics(uint64_t hash, const float *root, const 
                                         float *efforts, hipStream_t stream);
 int jit_launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n,
                           float *state, float *matrix, float *bias, hipStream_t stream);
+int jit_launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
+                           const ScanArgs &sa, float *heights, float *normals, hipStream_t stream);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

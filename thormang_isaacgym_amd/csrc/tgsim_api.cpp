@@ -907,6 +907,62 @@ int tg_centroidal(tg_sim *s, float *state, float *matrix, float *bias) {
     return TG_OK;
 }
 
+int tg_height_scan(tg_sim *s, const tg_contact_frame *frames, int32_t num_frames, const float *points,
+                   int32_t num_points, const tg_scan_params *params, float *heights, float *normals) {
+    const char *fn = "tg_height_scan";
+    // everything that can be judged without the sim first, then the sim, then the links against its model
+    if (!frames) return fail(TG_ERR_ARG, "%s: null frames", fn);
+    if (!points) return fail(TG_ERR_ARG, "%s: null points", fn);
+    if (!params) return fail(TG_ERR_ARG, "%s: null params", fn);
+    if (num_frames < 1 || num_frames > TG_SCAN_MAX_FRAMES)
+        return fail(TG_ERR_ARG, "%s: num_frames %d outside 1..%d", fn, num_frames, TG_SCAN_MAX_FRAMES);
+    if (num_points < 1 || num_points > TG_SCAN_MAX_POINTS)
+        return fail(TG_ERR_ARG, "%s: num_points %d outside 1..%d", fn, num_points, TG_SCAN_MAX_POINTS);
+    tg::ScanArgs sa{};
+    for (int k = 0; k < num_frames; ++k) {
+        if (frames[k].link < 0) return fail(TG_ERR_ARG, "%s: frame %d: link %d is negative", fn, k, frames[k].link);
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(frames[k].offset[i]))
+                return fail(TG_ERR_ARG, "%s: frame %d: offset[%d] is not finite", fn, k, i);
+        sa.f[k] = frames[k];
+    }
+    const tg_scan_params &p = *params;
+    if (p.surface != TG_SCAN_SURFACE && p.surface != TG_SCAN_CELL)
+        return fail(TG_ERR_ARG, "%s: surface %d is neither TG_SCAN_SURFACE nor TG_SCAN_CELL", fn, p.surface);
+    if (p.align != TG_SCAN_YAW && p.align != TG_SCAN_WORLD && p.align != TG_SCAN_LINK)
+        return fail(TG_ERR_ARG, "%s: align %d is none of TG_SCAN_YAW, TG_SCAN_WORLD, TG_SCAN_LINK", fn, p.align);
+    if (p.relative != 0) {
+        if (!std::isfinite(p.bias) || !std::isfinite(p.scale))
+            return fail(TG_ERR_ARG, "%s: relative with a non-finite bias %g or scale %g", fn, (double)p.bias,
+                        (double)p.scale);
+        if (!(p.lo <= p.hi))
+            return fail(TG_ERR_ARG, "%s: relative needs lo <= hi, got %g and %g", fn, (double)p.lo, (double)p.hi);
+    }
+    if (normals && p.surface == TG_SCAN_CELL)
+        return fail(TG_ERR_ARG, "%s: TG_SCAN_CELL has no normals: normals must be null", fn);
+    if (!heights && !normals) return fail(TG_ERR_ARG, "%s: heights and normals are both null", fn);
+    if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
+    for (int k = 0; k < num_frames; ++k)
+        if (frames[k].link >= s->L)
+            return fail(TG_ERR_ARG, "%s: frame %d: link %d outside [0, %d)", fn, k, frames[k].link, s->L);
+    sa.F = num_frames;
+    sa.P = num_points;
+    sa.p = p;
+    // the heightfield of this moment (step_args hands the step kernel the same members)
+    sa.hf = s->hf_rows > 0 ? s->hf : nullptr;
+    sa.hf_rows = s->hf_rows;
+    sa.hf_cols = s->hf_cols;
+    sa.hf_hs = s->hf_hs;
+    sa.hf_vs = s->hf_vs;
+    sa.hf_ox = s->hf_ox;
+    sa.hf_oy = s->hf_oy;
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_height_scan(s->hash, s->root, s->dof, points, (int)s->N, sa, heights, normals, s->stream))
+        return fail(rc, "%s: launch failed", fn);
+    return TG_OK;
+}
+
 int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
     if (int rc = check_sim(s)) return rc;
     if (!out) {

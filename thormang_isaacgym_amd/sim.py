@@ -139,6 +139,7 @@ def _ptr(t: torch.Tensor | None):
 
 Centroidal = namedtuple("Centroidal", ["state", "matrix", "bias"])   # what Sim.centroidal returns
 ContactDynamics = namedtuple("ContactDynamics", ["tau", "wrench"])   # what Sim.contact_inverse_dynamics returns
+HeightScan = namedtuple("HeightScan", ["heights", "normals"])   # what Sim.height_scan returns
 
 
 class Sim:
@@ -762,6 +763,95 @@ class Sim:
                       for key, asked in (("out", True), ("out_matrix", matrix), ("out_bias", bias)))
         check(lib().tg_centroidal(self._h, _ptr(st), _ptr(mt), _ptr(bt)), "centroidal")
         return Centroidal(st, mt, bt)
+
+    def scan_grid(self, xs, ys) -> torch.Tensor:
+        """The pattern ``[len(xs) * len(ys), 2]`` of ``height_scan`` over the
+        grid ``xs`` x ``ys`` (metres, in the frame's axes), float32 on the
+        sim's device, in the order of the reference's ``init_height_points``
+        (tasks/anymal_terrain.py:501-511): ``torch.meshgrid(x, y)`` with ij
+        indexing, flattened -- x varies slowest."""
+        x = torch.as_tensor(xs, dtype=torch.float32).reshape(-1)
+        y = torch.as_tensor(ys, dtype=torch.float32).reshape(-1)
+        gx, gy = torch.meshgrid(x, y, indexing="ij")
+        return torch.stack([gx.reshape(-1), gy.reshape(-1)], dim=1).contiguous().to(self.device)
+
+    def height_scan(self, frames, points: torch.Tensor, surface: str = "surface", align: str = "yaw",
+                    normals: bool = False, relative: dict | None = None, out: torch.Tensor | None = None,
+                    out_normals: torch.Tensor | None = None) -> "HeightScan":
+        """The ground under the robot in one kernel launch (tgsim.h
+        tg_height_scan), from the current state and the sim's heightfield, on
+        the sim's stream.  ``frames``: 1..8 ``contact_frame`` (a link, by name
+        or index, stands for its origin); ``points`` [P, 2] float32 on the
+        sim's device (``scan_grid``), one pattern for every env and frame,
+        P <= 1024.  Sample k of frame f lies at the frame point's world x, y
+        plus ``points[k]`` turned by the link's heading (``align="yaw"``, the
+        reference's ``quat_apply_yaw``), not at all (``"world"``), or laid out
+        in the link's own axes and dropped vertically (``"link"``).
+        ``surface="surface"`` reads the surface the contacts feel -- the
+        heightfield's triangles or the z = 0 plane, whichever is higher -- and
+        ``"cell"`` the reference's ``get_heights`` rule, the lower of two
+        corners of the cell (it has no normals).  Returns ``HeightScan(heights,
+        normals)``: ``heights`` [N, F, P]; with ``normals`` the unit surface
+        normals [N, F, P, 3], else None.  ``relative=dict(bias=, lo=, hi=,
+        scale=)`` turns the heights into ``clamp(p_f.z - bias - h, lo, hi) *
+        scale``, the reference's height observation (bias 0.5, -1, 1,
+        heightMeasurementScale) or a foot's clearance.  ``out`` and
+        ``out_normals`` are checked and, for a requested part, written and
+        returned as given; without them the tensors are owned by the sim and
+        overwritten by the next call with as many frames and points."""
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        def own(key, shape):
+            buf = getattr(self, "_scan_out", None)
+            if buf is None:
+                buf = self._scan_out = {}
+            if (key, shape) not in buf:
+                buf[key, shape] = torch.zeros(*shape, dtype=torch.float32, device=self.device)
+            return buf[key, shape]
+
+        rules = {"surface": abi.TG_SCAN_SURFACE, "cell": abi.TG_SCAN_CELL}
+        aligns = {"yaw": abi.TG_SCAN_YAW, "world": abi.TG_SCAN_WORLD, "link": abi.TG_SCAN_LINK}
+        if surface not in rules:
+            raise ValueError(f"surface must be one of {sorted(rules)}, got {surface!r}")
+        if align not in aligns:
+            raise ValueError(f"align must be one of {sorted(aligns)}, got {align!r}")
+        if normals and surface == "cell":
+            raise ValueError("the cell rule has no normals")
+        frames = [c if isinstance(c, abi.tg_contact_frame) else self.contact_frame(c) for c in frames]
+        F = len(frames)
+        if not 1 <= F <= abi.TG_SCAN_MAX_FRAMES:
+            raise ValueError(f"height_scan takes 1..{abi.TG_SCAN_MAX_FRAMES} frames, got {F}")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 2:
+            raise ValueError("points must be a [P, 2] tensor")
+        P = int(points.shape[0])
+        if not 1 <= P <= abi.TG_SCAN_MAX_POINTS:
+            raise ValueError(f"height_scan takes 1..{abi.TG_SCAN_MAX_POINTS} points, got {P}")
+        checked(points, (P, 2), "points")
+        N = self.num_envs
+        shapes = {"out": (N, F, P), "out_normals": (N, F, P, 3)}
+        given = {"out": out, "out_normals": out_normals}
+        for key, t in given.items():
+            if t is not None:
+                checked(t, shapes[key], key)
+        ht, nt = ((given[key] if given[key] is not None else own(key, shapes[key])) if asked else None
+                  for key, asked in (("out", True), ("out_normals", normals)))
+        sp = abi.tg_scan_params()
+        sp.surface, sp.align, sp.relative = rules[surface], aligns[align], 0
+        if relative is not None:
+            if set(relative) != {"bias", "lo", "hi", "scale"}:
+                raise ValueError("relative must be dict(bias=, lo=, hi=, scale=)")
+            sp.relative = 1
+            sp.bias, sp.lo, sp.hi, sp.scale = (float(relative[k]) for k in ("bias", "lo", "hi", "scale"))
+        arr = (abi.tg_contact_frame * F)(*frames)
+        check(lib().tg_height_scan(self._h, arr, F, _ptr(points), P, C.byref(sp), _ptr(ht), _ptr(nt)), "height_scan")
+        self._keep_scan_points = points   # read on the sim stream; held until the next call
+        return HeightScan(ht, nt)
 
     @property
     def contact_link_indices(self) -> list:

@@ -311,6 +311,13 @@ class VecTask(Env):
         (Sim.centroidal)."""
         return self.sim.centroidal(matrix=matrix, bias=bias, out=out, out_matrix=out_matrix, out_bias=out_bias)
 
+    def height_scan(self, frames, points, surface="surface", align="yaw", normals=False, relative=None, out=None,
+                    out_normals=None):
+        """Terrain heights [N, F, P] and optionally the surface normals [N, F, P, 3] under the pattern ``points``
+        [P, 2] about the link frames ``frames``, in one kernel (Sim.height_scan)."""
+        return self.sim.height_scan(frames, points, surface=surface, align=align, normals=normals, relative=relative,
+                                    out=out, out_normals=out_normals)
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)

@@ -24,6 +24,15 @@ Differences from the reference, all deliberate:
 * ``USE_TERAIN`` (:26, :157-181, :523-534) hands the Perlin height samples to
   the simulator (tg_set_heightfield) instead of a triangle mesh: the contact
   kernel evaluates that mesh's surface directly (tasks/terrain.py).
+
+``env.enableHeightScan: true`` (optional, default false) adds
+``extras["measured_heights"]`` [N,140] after every step -- the ground heights
+under the 14 x 10 pattern of the reference's ``init_height_points``
+(tasks/anymal_terrain.py:501-511) about the scooter's root link, turned by its
+heading, on the surface the contacts feel (tgsim.h tg_height_scan), of the
+state the step returns with: one extra kernel launch per step, zeros on the
+flat ground.  Observation, reward and reset do not read it, and the step itself
+is unchanged.
 """
 from __future__ import annotations
 
@@ -127,6 +136,14 @@ class Gogoro(VecTask):
             self.root_reset_tensor[:, 2] = self._terrain_spawn_z()
             self.params.terrain_spawn = 1
         self._bufs = self._make_buffers()
+        # env.enableHeightScan: the ground heights under the reference's 14 x 10 pattern about the scooter's root link,
+        # turned by its heading (tg_height_scan); observation, reward and reset do not use them
+        self.measured_heights = None
+        if bool(self.cfg["env"].get("enableHeightScan", False)):
+            self.height_points = self.sim.scan_grid(0.1 * torch.tensor(self.HEIGHT_SCAN_X, dtype=torch.float32),
+                                                    0.1 * torch.tensor(self.HEIGHT_SCAN_Y, dtype=torch.float32))
+            self._scan_frames = [self.sim.contact_frame(0)]
+            self.measured_heights = torch.zeros(self.n_envs, 1, self.height_points.shape[0], device=self.sim.device)
         self.reset_idx(torch.arange(0, self.n_envs, device=self.device).type(torch.long))
 
     # ------------------------------------------------------------ creation
@@ -146,6 +163,12 @@ class Gogoro(VecTask):
 
     #: grid pitch the terrain placement assumes (gogoro_new.py:171, = 2 x env_spacing)
     terrain_env_pitch = 2
+
+    #: the height-scan pattern of env.enableHeightScan, metres about the root link: the 14 x 10 points of the
+    #: reference's init_height_points (tasks/anymal_terrain.py:503-504), a 1.6 m x 1 m rectangle without centre lines
+    #: (in tenths of a metre; scaled in float32 as the reference does)
+    HEIGHT_SCAN_X = (-8, -7, -6, -5, -4, -3, -2, 2, 3, 4, 5, 6, 7, 8)
+    HEIGHT_SCAN_Y = (-5, -4, -3, -2, -1, 1, 2, 3, 4, 5)
 
     def _create_ground_plane(self):
         """The Perlin terrain beside the z = 0 plane (gogoro_new.py:164-181):
@@ -240,6 +263,11 @@ class Gogoro(VecTask):
         freq = self.randomization_params.get("frequency", 1)
         if self.frame_count - self.last_rand_step >= freq:
             self.apply_randomizations(self.randomization_params)
+        # extras["measured_heights"] [N, 140]: the height scan of the state the step returns with (env.enableHeightScan)
+        if getattr(self, "measured_heights", None) is not None:
+            self.height_scan(self._scan_frames, self.height_points, surface="surface", align="yaw",
+                             out=self.measured_heights)
+            self.extras["measured_heights"] = self.measured_heights[:, 0].to(self.rl_device)
 
     def compute_obs_rwd(self):
         """Fused into post_physics_step (tg_gogoro_post_physics); kept for API parity."""
