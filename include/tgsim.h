@@ -88,6 +88,11 @@
  *                            observation (tasks/anymal_terrain.py:501-536,
  *                            :301-302), about any link frames, on the surface the
  *                            contacts feel or by the reference's cell rule
+ *   tg_imu                   the inertial measurement unit the paper task observes
+ *                            ("imu" roll, yaw and their rates with an IMU noise
+ *                            and offset, tasks/gogoro_realistic_turning_sim_paper.py
+ *                            :55-67, :525-531): orientation, projected gravity,
+ *                            gyro and accelerometer readings at link frames
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -830,6 +835,75 @@ int tg_height_scan(tg_sim *sim, const tg_contact_frame *frames /* HOST */, int32
                    const tg_scan_params *params /* HOST */,
                    float *heights /* [N, F, P] device or NULL */,
                    float *normals /* [N, F, P, 3] device or NULL */);
+/* The inertial measurement unit in one kernel: orientation, projected gravity,
+ * body-frame velocities, gyro and accelerometer readings at up to
+ * TG_IMU_MAX_SENSORS link frames -- what the reference's paper task observes as
+ * "imu" roll, yaw and their rates with an IMU noise and an IMU offset
+ * (tasks/gogoro_realistic_turning_sim_paper.py:55-67, :525-531) and what every
+ * legged sim-to-real policy starts from.  On demand, stream-ordered, from the
+ * current root and dof state and the sim's gravity at the time of the call
+ * (tg_set_gravity is honoured); nothing of the sim is written and the library
+ * keeps nothing between calls: no host cache, no hidden step counter.  The
+ * previous velocities an accelerometer needs live in the caller-owned history
+ * tensor.
+ *
+ * Sensor s is the point
+ *   p_s = o_l + R_l offset_s
+ * on link l_s, the convention of tg_contact_frame, tg_set_force_sensor_tensor
+ * and tg_height_scan; a link may appear in several sensors.  Its axes are the
+ * link's.  From the current state
+ *   R   = R_l, the link's rotation (link to world)
+ *   w   = the link's world angular velocity, as tg_rigid_body_states reports it
+ *   v   = the world velocity of the material point p_s: the link origin's
+ *         velocity plus w x R_l offset_s.  (root_state[7:10] is the velocity
+ *         of the root link's centre of mass, as in tg_rigid_body_states.)
+ * and with g the sim's gravity, out[e, s, 0:TG_IMU_WIDTH] is
+ *   0:4    the link's world quaternion xyzw, as tg_rigid_body_states reports it
+ *   4:7    gravity_b = R^T g / |g|, zero when |g| = 0
+ *   7:10   lin_vel_b = R^T v
+ *   10:13  ang_vel_b = R^T w + bias[e, s, 0:3] + gyro_noise * n[0:3]
+ *   13:16  lin_acc_b = R^T (a - g) + bias[e, s, 3:6] + accel_noise * n[3:6],
+ *          the specific force: +|g| along world up at rest, 0 in free fall
+ *   16:19  ang_acc_b = R^T alpha
+ *   19     valid: 1.0 where a and alpha were differenced, else 0.0
+ * a = (v - v_prev) / dt and alpha = (w - w_prev) / dt, v_prev and w_prev from
+ * history [N, S, TG_IMU_HISTORY]: v world in slots 0:3, w world in slots 3:6,
+ * the valid flag in slot 6, slot 7 written 0.  a = alpha = 0 and valid = 0, so
+ * that the accelerometer reads -R^T g, whenever history is NULL, the history's
+ * flag is not 1.0, or reset[e] != 0.  After forming the outputs the call writes
+ * the current true (noise-free, bias-free) v, w and the flag 1.0 into history,
+ * reset envs included; the history is read before it is written.
+ *
+ * dt is the sim time since the history was written; the caller states it.
+ * reset is [N] int64 on the device or NULL, the dtype of VecTask.reset_buf and
+ * tg_walk_buffers.reset_buf; bias is [N, S, 6] on the device or NULL.  n are
+ * standard normals, drawn only when a sigma is non-zero: Philox block
+ * 3 (e S + s) + j, j = 0..2, has counter (block, counter lo, counter hi, 0) and
+ * key seed, and its two values gauss(x, y), gauss(z, w) are n[2j], n[2j+1] --
+ * exactly the blocks and functions of tg_rng_fill kind 2 with n = 3 N S.
+ *
+ * The link poses are formed relative to the root link's origin; no absolute
+ * position enters any output, so every output is bit-identical wherever the
+ * env stands.  Envs do not interact.  Every element of out is written.
+ *
+ * TG_ERR_ARG (message "tg_imu: ...") and nothing launched, in this order, for
+ * null sensors, params or out, num_sensors outside 1..TG_IMU_MAX_SENSORS, a
+ * negative link, a non-finite offset, a non-finite or negative sigma, a history
+ * given with a dt that is not finite and > 0, a null sim, a link >= L: what
+ * needs no sim first, then the sim, then the links.  Every model, run-time
+ * (tg_model_jit) ones included. */
+#define TG_IMU_MAX_SENSORS 8
+#define TG_IMU_WIDTH 20     /* floats per sensor reading   */
+#define TG_IMU_HISTORY 8    /* floats per sensor's history */
+typedef struct tg_imu_params {   /* HOST, read during the call */
+    float dt, gyro_noise, accel_noise;
+    int32_t pad;
+    uint64_t seed, counter;
+} tg_imu_params;                 /* 32 bytes */
+int tg_imu(tg_sim *sim, const tg_contact_frame *sensors /* HOST */, int32_t num_sensors,
+           const tg_imu_params *params /* HOST */, const float *bias /* [N, S, 6] device or NULL */,
+           const int64_t *reset /* [N] device or NULL */, float *history /* [N, S, 8] device or NULL */,
+           float *out /* [N, S, 20] device */);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

@@ -97,6 +97,18 @@ class tg_scan_params(C.Structure):
 
 assert C.sizeof(tg_scan_params) == 28
 
+TG_IMU_MAX_SENSORS = 8                  # sensors of tg_imu (they are tg_contact_frames too)
+TG_IMU_WIDTH, TG_IMU_HISTORY = 20, 8    # floats per sensor of tg_imu's out and history (tgsim.h)
+
+
+class tg_imu_params(C.Structure):
+    """The time step, the noise sigmas and the Philox seed and counter of tg_imu (tgsim.h)."""
+    _fields_ = [("dt", C.c_float), ("gyro_noise", C.c_float), ("accel_noise", C.c_float), ("pad", C.c_int32),
+                ("seed", C.c_uint64), ("counter", C.c_uint64)]
+
+
+assert C.sizeof(tg_imu_params) == 32
+
 
 class tg_osc_gains(C.Structure):
     """The gains of tg_osc (tgsim.h): task-space kp / kd, null-space kp_null / kd_null, the damping lambda."""

@@ -214,6 +214,14 @@ int launch_height_scan(uint64_t hash, const float *root, const float *dof, const
     }) ? rc : jit_launch_height_scan(hash, root, dof, points, n, sa, heights, normals, stream);
 }
 
+int launch_imu(uint64_t hash, const float *root, const float *dof, int n, const ImuArgs &ia, const float *bias,
+               const int64_t *reset, float *history, float *out, hipStream_t stream) {
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(imu_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, n, ia, bias, reset, history, out);
+    }) ? rc : jit_launch_imu(hash, root, dof, n, ia, bias, reset, history, out, stream);
+}
+
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {

@@ -2182,6 +2182,139 @@ __global__ __launch_bounds__(64) void height_scan_kernel(const float *root, cons
     }
 }
 
+// Inertial measurement units (tgsim.h tg_imu): out [N, S, 20] -- the link's
+// quaternion, the projected gravity, the body-frame velocities of the sensor
+// point, gyro and accelerometer readings, the angular acceleration and the
+// valid flag -- at S link frames, differenced against the caller's history
+// [N, S, 8] (world v, w, flag, 0), which is then rewritten.  One wavefront per
+// env:
+//   lanes < 3 S   one Philox block each, the two normals of block 3 (e S + s) + j
+//                 into LDS (only when a sigma is non-zero; uniform)
+//   lane = sensor asks for its history and bias rows and the root's velocity,
+//                 so that they arrive behind the forward kinematics
+//   lanes         forward kinematics (fk_root_relative)
+//   lane = sensor walks its link's ancestors once: w = w_root + sum qd_d a_d,
+//                 v = v_root_origin + w_root x p + sum qd_d a_d x (p - anchor_d)
+//                 (qd_d a_d for a prismatic joint), p the sensor point relative
+//                 to the root origin; forms the 20 outputs and the 8 history
+//                 floats in LDS
+//   lanes         stride over the S 20 and S 8 floats in output order, so that
+//                 the stores are contiguous
+// The history is read at the top, into the registers of the lanes that use it,
+// and stored at the bottom.  No absolute position enters.  Wave-level syncs
+// only, plain stores, no atomics.
+template <class M>
+__global__ __launch_bounds__(64) void imu_kernel(const float *root, const float *dof, int n, ImuArgs a,
+                                                 const float *bias, const int64_t *reset, float *history,
+                                                 float *out) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    __shared__ float T[M::NL][12], A[M::NL][3];
+    __shared__ float NZ[TG_IMU_MAX_SENSORS][6];
+    __shared__ float O[TG_IMU_MAX_SENSORS * TG_IMU_WIDTH], H[TG_IMU_MAX_SENSORS * TG_IMU_HISTORY];
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const int S = a.S;
+    const bool noisy = a.gyro_noise != 0.f || a.accel_noise != 0.f;
+    if (noisy && lane < 3 * S) {
+        const int s = lane / 3, j = lane - 3 * s;
+        const U4 x = philox(U4{(uint32_t)(3 * (e * S + s) + j), a.c_lo, a.c_hi, 0u}, a.k0, a.k1);
+        NZ[s][2 * j] = gauss(x.x, x.y);
+        NZ[s][2 * j + 1] = gauss(x.z, x.w);
+    }
+    const float *r = root + 13 * (size_t)e;
+    const float *q = dof + 2 * (size_t)e * M::ND;
+    // what the later phases read from global memory is asked for first, so that it arrives behind the forward
+    // kinematics: the sensor lanes' history row (read here, before anything of it is stored), bias row and the
+    // root's velocity, and each lane's links' dof velocities
+    const size_t row = (size_t)e * S + lane;
+    const bool sensor = lane < S;
+    const bool differenced = sensor && history && !(reset && reset[e] != 0);
+    float hp[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, bs[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, rv[6];
+    if (differenced) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) hp[k] = history[row * TG_IMU_HISTORY + k];
+    }
+    if (sensor && bias) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) bs[k] = bias[row * 6 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rv[k] = sensor ? r[7 + k] : 0.f;
+    fk_root_relative<M>(r, q, lane, T, A);   // (ends with a wave-level sync: NZ is visible too)
+    if (sensor) {
+        const int l = a.s[lane].link;
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const V3 p = v3(T[l][9], T[l][10], T[l][11]) +
+                     mul(R, v3(a.s[lane].offset[0], a.s[lane].offset[1], a.s[lane].offset[2]));
+        // the root's terms: root_state[7:10] is the velocity of the root link's com
+        M3 R0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R0.a[k] = T[0][k];
+        V3 w = v3(rv[3], rv[4], rv[5]);
+        const V3 c0 = v3(M::link_inertia[0][1], M::link_inertia[0][2], M::link_inertia[0][3]);
+        V3 v = v3(rv[0], rv[1], rv[2]) - cross(w, mul(R0, c0)) + cross(w, p);
+        for (int k = l; M::link_parent[k] >= 0; k = M::link_parent[k]) {
+            const int d = M::link_dof[k];
+            if (d < 0) continue;
+            const V3 qa = q[2 * d + 1] * v3(A[k][0], A[k][1], A[k][2]);
+            if (M::link_jtype[k] == TG_JOINT_REVOLUTE) {
+                w = w + qa;
+                v = v + cross(qa, p - v3(T[k][9], T[k][10], T[k][11]));
+            } else if (M::link_jtype[k] == TG_JOINT_PRISMATIC) {
+                v = v + qa;
+            }
+        }
+        // a = alpha = 0 without a valid history
+        V3 acc = v3(0.f, 0.f, 0.f), alpha = v3(0.f, 0.f, 0.f);
+        float valid = 0.f;
+        if (differenced && hp[6] == 1.f) {
+            valid = 1.f;
+            acc = v3((v.x - hp[0]) / a.dt, (v.y - hp[1]) / a.dt, (v.z - hp[2]) / a.dt);
+            alpha = v3((w.x - hp[3]) / a.dt, (w.y - hp[4]) / a.dt, (w.z - hp[5]) / a.dt);
+        }
+        const V3 g = v3(a.g[0], a.g[1], a.g[2]);
+        const float g2 = dot(g, g);
+        const V3 gb = g2 > 0.f ? mulT(R, (1.f / sqrtf(g2)) * g) : v3(0.f, 0.f, 0.f);
+        const V3 vb = mulT(R, v), ab = mulT(R, alpha);
+        V3 wb = mulT(R, w), fb = mulT(R, acc - g);
+        if (bias) {
+            wb = wb + v3(bs[0], bs[1], bs[2]);
+            fb = fb + v3(bs[3], bs[4], bs[5]);
+        }
+        if (noisy) {
+            wb = wb + a.gyro_noise * v3(NZ[lane][0], NZ[lane][1], NZ[lane][2]);
+            fb = fb + a.accel_noise * v3(NZ[lane][3], NZ[lane][4], NZ[lane][5]);
+        }
+        float *o = O + lane * TG_IMU_WIDTH;
+        m3_to_quat(R, o[0], o[1], o[2], o[3]);
+        o[4] = gb.x; o[5] = gb.y; o[6] = gb.z;
+        o[7] = vb.x; o[8] = vb.y; o[9] = vb.z;
+        o[10] = wb.x; o[11] = wb.y; o[12] = wb.z;
+        o[13] = fb.x; o[14] = fb.y; o[15] = fb.z;
+        o[16] = ab.x; o[17] = ab.y; o[18] = ab.z;
+        o[19] = valid;
+        float *hn = H + lane * TG_IMU_HISTORY;
+        hn[0] = v.x; hn[1] = v.y; hn[2] = v.z;
+        hn[3] = w.x; hn[4] = w.y; hn[5] = w.z;
+        hn[6] = 1.f; hn[7] = 0.f;
+    }
+    wsync();
+    float *og = out + (size_t)e * S * TG_IMU_WIDTH;
+    for (int i = lane; i < S * TG_IMU_WIDTH; i += 64) og[i] = O[i];
+    if (history) {
+        float *hg = history + (size_t)e * S * TG_IMU_HISTORY;
+        for (int i = lane; i < S * TG_IMU_HISTORY; i += 64) hg[i] = H[i];
+    }
+}
+
 // ---------------------------------------------------------------- rigid-body forces
 // apply_rigid_body_force_tensors (reference call site
 // tasks/gogoro_realistic_turning_sim_paper.py:457): per-link forces [N*L,3] at

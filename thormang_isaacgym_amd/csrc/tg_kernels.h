@@ -52,6 +52,16 @@ struct ScanArgs {
     float hf_hs, hf_vs, hf_ox, hf_oy;
 };
 
+// what a tg_imu call hands imu_kernel by value: the sensors, their count, the sim's gravity at the time of the call,
+// dt, the sigmas and the Philox key and counter words of tg_imu_params
+struct ImuArgs {
+    tg_contact_frame s[TG_IMU_MAX_SENSORS];
+    int S;
+    float g[3];
+    float dt, gyro_noise, accel_noise;
+    uint32_t k0, k1, c_lo, c_hi;
+};
+
 // the sensors of tg_set_force_sensor_tensor as the step kernel takes them by value (step_par.h NoPostFS): the
 // frames as registered, their count and the axes of the output (TG_ENV_SPACE / TG_LOCAL_SPACE)
 struct FsFrames {
@@ -259,6 +269,10 @@ int launch_centroidal(uint64_t hash, const float *root, const float *dof, const 
 // frames (height_scan_kernel; tgsim.h tg_height_scan)
 int launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
                        const ScanArgs &sa, float *heights, float *normals, hipStream_t stream);
+// IMU readings [N, S, 20] at S link frames, differenced against and written into history [N, S, 8] (optional, as
+// bias [N, S, 6] and reset [N]) (imu_kernel; tgsim.h tg_imu)
+int launch_imu(uint64_t hash, const float *root, const float *dof, int n, const ImuArgs &ia, const float *bias,
+               const int64_t *reset, float *history, float *out, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
@@ -306,6 +320,8 @@ int jit_launch_centroidal(uint64_t hash, const float *root, const float *dof, co
                           float *state, float *matrix, float *bias, hipStream_t stream);
 int jit_launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
                            const ScanArgs &sa, float *heights, float *normals, hipStream_t stream);
+int jit_launch_imu(uint64_t hash, const float *root, const float *dof, int n, const ImuArgs &ia, const float *bias,
+                   const int64_t *reset, float *history, float *out, hipStream_t stream);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

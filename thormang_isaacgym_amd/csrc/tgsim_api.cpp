@@ -963,6 +963,50 @@ int tg_height_scan(tg_sim *s, const tg_contact_frame *frames, int32_t num_frames
     return TG_OK;
 }
 
+int tg_imu(tg_sim *s, const tg_contact_frame *sensors, int32_t num_sensors, const tg_imu_params *params,
+           const float *bias, const int64_t *reset, float *history, float *out) {
+    const char *fn = "tg_imu";
+    // everything that can be judged without the sim first, then the sim, then the links against its model
+    if (!sensors) return fail(TG_ERR_ARG, "%s: null sensors", fn);
+    if (!params) return fail(TG_ERR_ARG, "%s: null params", fn);
+    if (!out) return fail(TG_ERR_ARG, "%s: null out", fn);
+    if (num_sensors < 1 || num_sensors > TG_IMU_MAX_SENSORS)
+        return fail(TG_ERR_ARG, "%s: num_sensors %d outside 1..%d", fn, num_sensors, TG_IMU_MAX_SENSORS);
+    tg::ImuArgs ia{};
+    for (int k = 0; k < num_sensors; ++k) {
+        if (sensors[k].link < 0) return fail(TG_ERR_ARG, "%s: sensor %d: link %d is negative", fn, k, sensors[k].link);
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(sensors[k].offset[i]))
+                return fail(TG_ERR_ARG, "%s: sensor %d: offset[%d] is not finite", fn, k, i);
+        ia.s[k] = sensors[k];
+    }
+    const tg_imu_params &p = *params;
+    if (!std::isfinite(p.gyro_noise) || p.gyro_noise < 0.f)
+        return fail(TG_ERR_ARG, "%s: gyro_noise %g is not a finite number >= 0", fn, (double)p.gyro_noise);
+    if (!std::isfinite(p.accel_noise) || p.accel_noise < 0.f)
+        return fail(TG_ERR_ARG, "%s: accel_noise %g is not a finite number >= 0", fn, (double)p.accel_noise);
+    if (history && !(std::isfinite(p.dt) && p.dt > 0.f))
+        return fail(TG_ERR_ARG, "%s: history with a dt %g that is not a finite number > 0", fn, (double)p.dt);
+    if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
+    for (int k = 0; k < num_sensors; ++k)
+        if (sensors[k].link >= s->L)
+            return fail(TG_ERR_ARG, "%s: sensor %d: link %d outside [0, %d)", fn, k, sensors[k].link, s->L);
+    ia.S = num_sensors;
+    memcpy(ia.g, s->gravity, sizeof ia.g);   // the gravity of this moment
+    ia.dt = p.dt;
+    ia.gyro_noise = p.gyro_noise;
+    ia.accel_noise = p.accel_noise;
+    ia.k0 = (uint32_t)p.seed;
+    ia.k1 = (uint32_t)(p.seed >> 32);
+    ia.c_lo = (uint32_t)p.counter;
+    ia.c_hi = (uint32_t)(p.counter >> 32);
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_imu(s->hash, s->root, s->dof, (int)s->N, ia, bias, reset, history, out, s->stream))
+        return fail(rc, "%s: launch failed", fn);
+    return TG_OK;
+}
+
 int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
     if (int rc = check_sim(s)) return rc;
     if (!out) {

@@ -140,6 +140,8 @@ def _ptr(t: torch.Tensor | None):
 Centroidal = namedtuple("Centroidal", ["state", "matrix", "bias"])   # what Sim.centroidal returns
 ContactDynamics = namedtuple("ContactDynamics", ["tau", "wrench"])   # what Sim.contact_inverse_dynamics returns
 HeightScan = namedtuple("HeightScan", ["heights", "normals"])   # what Sim.height_scan returns
+# what Sim.imu returns: views of raw [N, S, 20]
+Imu = namedtuple("Imu", ["quat", "gravity", "lin_vel", "ang_vel", "lin_acc", "ang_acc", "valid", "raw"])
 
 
 class Sim:
@@ -852,6 +854,84 @@ class Sim:
         check(lib().tg_height_scan(self._h, arr, F, _ptr(points), P, C.byref(sp), _ptr(ht), _ptr(nt)), "height_scan")
         self._keep_scan_points = points   # read on the sim stream; held until the next call
         return HeightScan(ht, nt)
+
+    def imu_history(self, num_sensors: int) -> torch.Tensor:
+        """A fresh history tensor for ``imu``: zeros [N, num_sensors, 8] on the
+        sim's device.  Its flag is 0, so the first reading comes out with
+        ``valid = 0``."""
+        S = int(num_sensors)
+        if not 1 <= S <= abi.TG_IMU_MAX_SENSORS:
+            raise ValueError(f"imu takes 1..{abi.TG_IMU_MAX_SENSORS} sensors, got {S}")
+        return torch.zeros(self.num_envs, S, abi.TG_IMU_HISTORY, dtype=torch.float32, device=self.device)
+
+    def imu(self, sensors, history: torch.Tensor | None = None, dt: float | None = None,
+            reset: torch.Tensor | None = None, bias: torch.Tensor | None = None, gyro_noise: float = 0.0,
+            accel_noise: float = 0.0, seed: int = 0, counter: int = 0, out: torch.Tensor | None = None) -> "Imu":
+        """Inertial measurement units in one kernel launch (tgsim.h tg_imu), from
+        the current state and the sim's gravity, on the sim's stream.
+        ``sensors``: 1..8 ``contact_frame`` (a link, by name or index, stands
+        for its origin); the sensor's axes are the link's.  Returns the named
+        tuple ``Imu(quat, gravity, lin_vel, ang_vel, lin_acc, ang_acc, valid,
+        raw)`` of views of ``raw`` [N, S, 20]: the link's world quaternion xyzw,
+        the unit gravity direction, the sensor point's velocity, the gyro
+        reading, the accelerometer reading (the specific force: ``+|g|`` along
+        world up at rest, 0 in free fall) and the angular acceleration, all in
+        the link's axes, and ``valid`` [N, S], 1.0 where the accelerations were
+        differenced.  ``history`` [N, S, 8] (``imu_history``) is owned by the
+        caller: it holds the world velocities of the previous call, which the
+        accelerations are differenced against over ``dt`` -- the sim time since
+        that call, by default the sim params' ``dt``, one ``simulate`` -- and
+        is rewritten by this call.  Without a history, with a fresh one, and for
+        the envs flagged in ``reset`` ([N] int64, a ``reset_buf``), the
+        accelerations are 0, ``valid`` is 0 and the accelerometer reads
+        ``-R^T g``.  ``bias`` [N, S, 6] is added to the gyro (0:3) and
+        accelerometer (3:6) readings, and ``gyro_noise`` / ``accel_noise`` are
+        the sigmas of Gaussian noise on them, the Philox draws of ``tg_rng_fill``
+        kind 2 for (``seed``, ``counter``): pass a new ``counter`` every call.
+        ``out`` is checked, written and returned as ``raw``; without it the
+        tensor is owned by the sim and overwritten by the next call with as
+        many sensors."""
+        def checked(t, shape, what, dtype=torch.float32):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a {str(dtype).split('.')[-1]} tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        sensors = [c if isinstance(c, abi.tg_contact_frame) else self.contact_frame(c) for c in sensors]
+        S = len(sensors)
+        if not 1 <= S <= abi.TG_IMU_MAX_SENSORS:
+            raise ValueError(f"imu takes 1..{abi.TG_IMU_MAX_SENSORS} sensors, got {S}")
+        N = self.num_envs
+        if history is not None:
+            checked(history, (N, S, abi.TG_IMU_HISTORY), "history")
+        if reset is not None:
+            checked(reset, (N,), "reset", torch.int64)
+        if bias is not None:
+            checked(bias, (N, S, 6), "bias")
+        if out is not None:
+            raw = checked(out, (N, S, abi.TG_IMU_WIDTH), "out")
+        else:
+            buf = getattr(self, "_imu_out", None)
+            if buf is None:
+                buf = self._imu_out = {}
+            if S not in buf:
+                buf[S] = torch.zeros(N, S, abi.TG_IMU_WIDTH, dtype=torch.float32, device=self.device)
+            raw = buf[S]
+        ip = abi.tg_imu_params()
+        ip.dt = float(self.params.dt if dt is None else dt)
+        ip.gyro_noise, ip.accel_noise = float(gyro_noise), float(accel_noise)
+        ip.seed, ip.counter = int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1)
+        arr = (abi.tg_contact_frame * S)(*sensors)
+        check(lib().tg_imu(self._h, arr, S, C.byref(ip), _ptr(bias), _ptr(reset), _ptr(history), _ptr(raw)), "imu")
+        self._keep_imu = (bias, reset)   # read on the sim stream; held until the next call
+        # the views of the last raw tensor are kept: a task reads into the same one every step
+        views = getattr(self, "_imu_views", None)
+        if views is None or views.raw is not raw:
+            views = self._imu_views = Imu(raw[..., 0:4], raw[..., 4:7], raw[..., 7:10], raw[..., 10:13],
+                                          raw[..., 13:16], raw[..., 16:19], raw[..., 19], raw)
+        return views
 
     @property
     def contact_link_indices(self) -> list:

@@ -318,6 +318,13 @@ class VecTask(Env):
         return self.sim.height_scan(frames, points, surface=surface, align=align, normals=normals, relative=relative,
                                     out=out, out_normals=out_normals)
 
+    def imu(self, sensors, history=None, dt=None, reset=None, bias=None, gyro_noise=0.0, accel_noise=0.0, seed=0,
+            counter=0, out=None):
+        """IMU readings [N, S, 20] at the link frames ``sensors`` -- quaternion, projected gravity, body-frame
+        velocities, gyro, accelerometer, angular acceleration, valid flag -- in one kernel (Sim.imu)."""
+        return self.sim.imu(sensors, history=history, dt=dt, reset=reset, bias=bias, gyro_noise=gyro_noise,
+                            accel_noise=accel_noise, seed=seed, counter=counter, out=out)
+
     def step(self, actions: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self.dr_randomizations.get("actions", None):
             actions = self.dr_randomizations["actions"]["noise_lambda"](actions)

@@ -45,6 +45,21 @@ the model's shape -- in the foot link's own axes: ``force_sensors`` [N,2,6] and
 foot and its moment about the sole centre, for centre-of-pressure, ZMP or
 torsional-load terms a user adds.  Observation, reward and reset do not read
 them.  The step runs unfused as above.
+
+``env.enableImu: true`` (optional, default false) adds ``extras["imu"]``
+[N,1,20] after every step -- the reading of an inertial measurement unit at
+``imu_link`` (tgsim.h tg_imu): the link's quaternion, the projected gravity,
+the body-frame velocities, the gyro and accelerometer readings, the angular
+acceleration and the valid flag, differenced over ``dt = sim dt x
+controlFrequencyInv`` against a history the task keeps, one extra kernel
+launch per step.  The masked resets run inside the post-physics kernel
+(walk_post_kernel, csrc/walk_task.hip), driven by the ``reset_buf`` the step
+before left, which that kernel then overwrites; so the task hands tg_imu a copy
+of ``reset_buf`` taken before the step, and an env that was reset during the
+step reads ``valid = 0`` and zero accelerations instead of the jump.  An env
+reset through ``reset_idx`` from outside has its history dropped, to the same
+effect.  Observation, reward and reset do not read the extra, and the step
+itself is unchanged.
 """
 from __future__ import annotations
 
@@ -130,6 +145,14 @@ class ThormangWalk(VecTask):
         self.centroidal_state = None
         if bool(env.get("enableCentroidalState", False)):
             self.centroidal_state = torch.zeros(N, abi.TG_CENTROIDAL_STATE, device=dev)
+        # env.enableImu: orientation, projected gravity, gyro and accelerometer at imu_link of the state a step
+        # returns with (tg_imu); observation, reward and reset do not use them
+        self.imu_raw = None
+        if bool(env.get("enableImu", False)):
+            self._imu_sensors = [self.sim.contact_frame("imu_link")]
+            self.imu_history = self.sim.imu_history(1)
+            self.imu_raw = torch.zeros(N, 1, abi.TG_IMU_WIDTH, device=dev)
+            self._imu_reset = torch.zeros(N, dtype=torch.int64, device=dev)
         self.reset_idx(torch.arange(N, device=dev))
 
     # ------------------------------------------------------------ creation
@@ -174,6 +197,7 @@ class ThormangWalk(VecTask):
     # ------------------------------------------------------------ hot path
     def pre_physics_step(self, actions):
         a = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        self._imu_mark_resets()
         check(lib().tg_walk_pre_physics(self.sim.handle, C.byref(self.params), C.byref(self._bufs), _p(a)),
               "tg_walk_pre_physics")
         self._keep = a
@@ -217,6 +241,20 @@ class ThormangWalk(VecTask):
         # extras["centroidal"] [N, 16]: the centroidal state (env.enableCentroidalState)
         if getattr(self, "centroidal_state", None) is not None:
             self.extras["centroidal"] = self.centroidal(out=self.centroidal_state).state.to(self.rl_device)
+        # extras["imu"] [N, 1, 20]: the IMU reading at imu_link (env.enableImu)
+        if getattr(self, "imu_raw", None) is not None:
+            self.sim.imu(self._imu_sensors, history=self.imu_history, dt=self.dt, reset=self._imu_reset,
+                         out=self.imu_raw)
+            self.extras["imu"] = self.imu_raw.to(self.rl_device)
+
+    def _imu_mark_resets(self):
+        """The envs the coming step resets, for its IMU reading (env.enableImu): ``reset_buf`` as it stands before
+        the step.  The masked resets run inside the post-physics kernel (walk_post_kernel, csrc/walk_task.hip),
+        which reads the ``reset_buf`` the step before left, replaces the state of the flagged envs and then
+        writes the new flags -- so after the step ``reset_buf`` no longer says which envs jumped.  Their velocity
+        difference over the step is not an acceleration: tg_imu reports them with ``valid = 0``."""
+        if getattr(self, "imu_raw", None) is not None:
+            self._imu_reset.copy_(self.reset_buf)
 
     def step(self, actions):
         if self.dr_randomizations.get("actions", None) or self.dr_randomizations.get("observations", None):
@@ -227,6 +265,7 @@ class ThormangWalk(VecTask):
         # post kernel, so the replay draws are taken first
         a = actions.to(device=self.device, dtype=torch.float32).contiguous()
         rd, pd = self._post_draws()
+        self._imu_mark_resets()
         check(lib().tg_walk_step(self.sim.handle, C.byref(self.params), C.byref(self._bufs), _p(a),
                                  self.control_freq_inv, _p(rd), _p(pd), self._counter()), "tg_walk_step")
         self.frame_count += self.control_freq_inv
@@ -246,6 +285,9 @@ class ThormangWalk(VecTask):
         check(lib().tg_walk_reset_idx(self.sim.handle, C.byref(self.params), C.byref(self._bufs), _p(ids32), n,
                                       _p(rd), self._counter()), "tg_walk_reset_idx")
         self._keep_reset = (ids32, rd)
+        # an env reset from outside jumps too: its IMU history is dropped, so its next reading has valid = 0
+        if getattr(self, "imu_raw", None) is not None:
+            self.imu_history[env_ids.long()] = 0.0
 
 
 def walk_model_name(cfg) -> str:
