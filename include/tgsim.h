@@ -93,6 +93,9 @@
  *                            and offset, tasks/gogoro_realistic_turning_sim_paper.py
  *                            :55-67, :525-531): orientation, projected gravity,
  *                            gyro and accelerometer readings at link frames
+ *   tg_ray_cast              (no counterpart) lidar and depth-camera ranges: rays
+ *                            cast from link frames against the heightfield
+ *                            solid and the z = 0 plane
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -904,6 +907,86 @@ int tg_imu(tg_sim *sim, const tg_contact_frame *sensors /* HOST */, int32_t num_
            const tg_imu_params *params /* HOST */, const float *bias /* [N, S, 6] device or NULL */,
            const int64_t *reset /* [N] device or NULL */, float *history /* [N, S, 8] device or NULL */,
            float *out /* [N, S, 20] device */);
+/* Range sensing in one kernel: the distance along each ray of a pattern, and
+ * optionally the surface normal where it lands, cast from up to
+ * TG_RAY_MAX_FRAMES link frames against the ground -- a lidar ring, a
+ * forward-looking depth image, anything tg_height_scan's straight-down lookup
+ * cannot give.  On demand, stream-ordered, from the current root and dof state
+ * and the heightfield the sim holds at the time of the call
+ * (tg_set_heightfield; a later change, removal with rows = 0 included, is seen
+ * by the next call); nothing of the sim is written and nothing is kept on the
+ * host between calls.  A NULL output is not touched; every element of every
+ * non-NULL output is written.
+ *
+ * Frame f is the point
+ *   p_f = o_l + R_l offset_f
+ * on link l_f, as in tg_height_scan (tg_contact_frame; o_l and R_l those of
+ * tg_rigid_body_states); a link may appear in several frames.  rays [R, 6] is
+ * one pattern for every env and frame: rays[k] = (s_k, d_k), a start offset
+ * and a direction in the pattern's axes.  With the alignment matrix
+ *   TG_RAY_LINK   A = R_l, the link's own axes (its full 3-D rotation)
+ *   TG_RAY_YAW    A = Rz(psi), tg_height_scan's rule: (cos psi, sin psi) is
+ *                 (R00 + R11, R10 - R01) normalised; the identity when both
+ *                 are 0
+ *   TG_RAY_WORLD  A = I
+ * the world ray is
+ *   x(t) = p_f + A s_k + t A d_k,   t >= 0.
+ * d_k is NOT normalised by the call and t is the ray parameter: with unit
+ * directions t is the range; with a pinhole pattern scaled to d.x = 1 it is
+ * the depth along the optical axis.  max_range bounds t.
+ *
+ * The ground is the solid under the surface the contacts feel.  H(x, y) is the
+ * triangle height of tg_set_heightfield -- the cell split and the fu >= fv rule
+ * of ground_at -- defined on the closed grid rectangle
+ * [ox, ox + (rows - 1) hs] x [oy, oy + (cols - 1) hs] only, and
+ *   G = {z <= 0}  u  {(x, y) on the grid and z <= H(x, y)}
+ * (without a heightfield, the half-space alone).  Then
+ *   dist[e, f, k] = inf {t in [0, max_range] : x(t) in G},
+ * and max_range exactly when there is no such t (a miss): the ray hit
+ * something iff dist < max_range.  normals[e, f, k] is
+ *   e_z                       when the half-space z <= 0 is entered first
+ *   the triangle's unit       when the terrain solid is entered through a
+ *   normal (ground_at's)      triangle
+ *   (+-1, 0, 0), (0, +-1, 0)  at the grid's border the surface drops to the
+ *                             plane: a ray that enters the terrain solid
+ *                             through that vertical face reports the face's
+ *                             outward normal; the x face wins at a corner
+ *   ground_at's normal at     for a ray that starts inside G (dist = 0)
+ *   the start's (x, y)
+ *   (0, 0, 0)                 on a miss
+ * A ray with a zero or non-finite direction or start, or cast from a
+ * non-finite state, reads a miss.  (Finite input so large that the world ray
+ * overflows fp32 -- coordinates near 1e38 -- is not promised a miss; the call
+ * stays memory-safe and bounded.)  Hits on the robot's own links, on other envs
+ * and on the tyres are not modelled.
+ *
+ * The link poses are formed relative to the root link's origin and the root
+ * position is added last, as in tg_height_scan; p_f agrees with
+ * tg_rigid_body_states to rounding.  Envs do not interact: an env's results do
+ * not depend on the other envs' states.  The walk over the heightfield's cells
+ * is bounded by rows + cols + 4 cells per ray whatever the input.
+ *
+ * TG_ERR_ARG (message "tg_ray_cast: ...") with nothing launched, in this
+ * order: null frames, rays or params, dist and normals both NULL, num_frames
+ * outside 1..TG_RAY_MAX_FRAMES, num_rays outside 1..TG_RAY_MAX_RAYS, a
+ * negative link, a non-finite offset, align outside {0, 1, 2}, a max_range
+ * that is not finite and > 0, a null sim, a link >= L: what needs no sim
+ * first, then the sim, then the links.  Every model, run-time (tg_model_jit)
+ * ones included. */
+#define TG_RAY_MAX_FRAMES 8
+#define TG_RAY_MAX_RAYS   4096          /* per frame */
+#define TG_RAY_LINK  0   /* pattern in the link's own axes (full 3-D rotation R_l) */
+#define TG_RAY_YAW   1   /* pattern turned by the link's heading Rz(psi), tg_height_scan's rule */
+#define TG_RAY_WORLD 2   /* pattern in world axes */
+typedef struct tg_ray_params {   /* HOST, read during the call */
+    int32_t align;
+    float max_range;
+} tg_ray_params;                 /* 8 bytes */
+int tg_ray_cast(tg_sim *sim, const tg_contact_frame *frames /* HOST */, int32_t num_frames,
+                const float *rays /* [R, 6] device */, int32_t num_rays,
+                const tg_ray_params *params /* HOST */,
+                float *dist /* [N, F, R] device or NULL */,
+                float *normals /* [N, F, R, 3] device or NULL */);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

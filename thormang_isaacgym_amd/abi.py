@@ -109,6 +109,17 @@ class tg_imu_params(C.Structure):
 
 assert C.sizeof(tg_imu_params) == 32
 
+TG_RAY_MAX_FRAMES, TG_RAY_MAX_RAYS = 8, 4096    # frames (tg_contact_frames too) and rays per frame of tg_ray_cast
+TG_RAY_LINK, TG_RAY_YAW, TG_RAY_WORLD = 0, 1, 2  # the axes the ray pattern is given in
+
+
+class tg_ray_params(C.Structure):
+    """The alignment and the bound on the ray parameter of tg_ray_cast (tgsim.h)."""
+    _fields_ = [("align", C.c_int32), ("max_range", C.c_float)]
+
+
+assert C.sizeof(tg_ray_params) == 8
+
 
 class tg_osc_gains(C.Structure):
     """The gains of tg_osc (tgsim.h): task-space kp / kd, null-space kp_null / kd_null, the damping lambda."""

@@ -222,6 +222,15 @@ int launch_imu(uint64_t hash, const float *root, const float *dof, int n, const 
     }) ? rc : jit_launch_imu(hash, root, dof, n, ia, bias, reset, history, out, stream);
 }
 
+int launch_ray_cast(uint64_t hash, const float *root, const float *dof, const float *rays, int n, const RayArgs &ra,
+                    float *dist, float *normals, hipStream_t stream) {
+    int rc = 0;
+    return with_model(hash, [&](auto m) {
+        rc = run(ray_cast_kernel<decltype(m)>, dim3((unsigned)n * (unsigned)ray_chunks(ra)), dim3(64), stream, root,
+                 dof, rays, n, ra, dist, normals);
+    }) ? rc : jit_launch_ray_cast(hash, root, dof, rays, n, ra, dist, normals, stream);
+}
+
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {

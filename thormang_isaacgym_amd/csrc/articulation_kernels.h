@@ -2315,6 +2315,107 @@ __global__ __launch_bounds__(64) void imu_kernel(const float *root, const float 
     }
 }
 
+// Ray cast (tgsim.h tg_ray_cast): the ray parameter at which each of R pattern
+// rays, cast from F link frames, enters the ground solid, dist [N, F, R], and
+// optionally the normal there, normals [N, F, R, 3].  A pattern has up to 4096
+// rays per frame, far more than the 64 lanes of the one wavefront per env that
+// the other sensors use, so the F R samples of an env are spread over blocks
+// of one wavefront: block (env, chunk) takes RAY_CHUNK = 256 consecutive
+// samples in output order, four passes of 64 lanes, neighbouring rays of the
+// pattern in neighbouring lanes (they walk neighbouring cells and diverge
+// least).  After the clip to the highest vertex a ray walks few cells (1.4 to
+// 2.9 on average in scripts/ray_cast_bench.py's scenes), so the forward
+// kinematics that every block redoes, in order that blocks share nothing, is
+// the larger part of a small pattern's cost and is amortised over 256 rays in
+// a large one:
+//   lanes        forward kinematics (fk_root_relative)
+//   lane = frame the frame point p_f = o_l + R_l offset_f, relative to the root
+//                origin with the root position added last, and the alignment
+//                matrix A (R_l, Rz(psi) by height_scan_kernel's rule, or I):
+//                twelve floats per frame in LDS
+//   lanes        per sample: the world ray o = p_f + A s, d = A d_k, then
+//                ground_ray (ground.h); a non-finite entry of the frame or of
+//                the pattern is found on the words as loaded and makes a miss
+// Which outputs are null and the alignment are uniform over the launch.  Every
+// index into the table is clamped to the grid and the walk is bounded by an
+// integer counter (ground_ray).  Wave-level syncs only, plain stores, no
+// atomics, nothing shared between blocks.
+template <class M>
+__global__ __launch_bounds__(64) void ray_cast_kernel(const float *root, const float *dof, const float *rays, int n,
+                                                      RayArgs a, float *dist, float *normals) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    const int chunks = ray_chunks(a);
+    const int e = blockIdx.x / chunks, chunk = blockIdx.x - e * chunks;
+    if (e >= n) return;
+    __shared__ float T[M::NL][12], A[M::NL][3];
+    // p_f (3), the rows of A (9): kept as bits, so that a ray's test for a non-finite frame or pattern entry is an
+    // integer test on loaded words, which no floating-point assumption of the unit can fold away
+    __shared__ __align__(16) unsigned FR[TG_RAY_MAX_FRAMES][12];
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e;
+    fk_root_relative<M>(r, dof + 2 * (size_t)e * M::ND, lane, T, A);
+    if (lane < a.F) {
+        const int l = a.f[lane].link;
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const V3 p = v3(T[l][9], T[l][10], T[l][11]) +
+                     mul(R, v3(a.f[lane].offset[0], a.f[lane].offset[1], a.f[lane].offset[2]));
+        M3 Q = eye3();
+        if (a.align == TG_RAY_LINK) {
+            Q = R;
+        } else if (a.align == TG_RAY_YAW) {
+            const float c = R.a[0] + R.a[4], s = R.a[3] - R.a[1], d2 = c * c + s * s;
+            if (d2 > 0.f) {
+                const float in = rsqrtf(d2);
+                Q.a[0] = c * in; Q.a[1] = -(s * in); Q.a[3] = s * in; Q.a[4] = c * in;
+            }
+        }
+        // the root position is added last: the relative frame point does not depend on where the env sits
+        unsigned *o = FR[lane];
+        o[0] = __float_as_uint(r[0] + p.x); o[1] = __float_as_uint(r[1] + p.y); o[2] = __float_as_uint(r[2] + p.z);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o[3 + k] = __float_as_uint(Q.a[k]);
+    }
+    wsync();
+    const int R = a.R, S = a.F * R;
+    const size_t base = (size_t)e * S;
+    const unsigned *rp = reinterpret_cast<const unsigned *>(rays);   // words, four-byte aligned as any float array
+    const int end = min(S, (chunk + 1) * RAY_CHUNK);
+    for (int s = chunk * RAY_CHUNK + lane; s < end; s += 64) {
+        const int f = s / R, k = s - f * R;
+        const unsigned *rk = rp + 6 * (size_t)k;
+        const uint2 r0 = make_uint2(rk[0], rk[1]), r1 = make_uint2(rk[2], rk[3]),
+                    r2 = make_uint2(rk[4], rk[5]);                      // s.x s.y | s.z d.x | d.y d.z
+        const unsigned *fr = FR[f];
+        bool finite = ground_finite_bits(r0.x) && ground_finite_bits(r0.y) && ground_finite_bits(r1.x) &&
+                      ground_finite_bits(r1.y) && ground_finite_bits(r2.x) && ground_finite_bits(r2.y);
+        M3 Q;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            finite = finite && ground_finite_bits(fr[3 + q]);
+            Q.a[q] = __uint_as_float(fr[3 + q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) finite = finite && ground_finite_bits(fr[q]);
+        const V3 o = v3(__uint_as_float(fr[0]), __uint_as_float(fr[1]), __uint_as_float(fr[2])) +
+                     mul(Q, v3(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r1.x)));
+        const V3 d = mul(Q, v3(__uint_as_float(r1.y), __uint_as_float(r2.x), __uint_as_float(r2.y)));
+        V3 nn;
+        const float t = ground_ray(a, o, d, a.max_range, finite, nn);
+        if (dist) dist[base + s] = t;
+        if (normals) {
+            float *w = normals + (base + s) * 3;
+            w[0] = nn.x; w[1] = nn.y; w[2] = nn.z;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- rigid-body forces
 // apply_rigid_body_force_tensors (reference call site
 // tasks/gogoro_realistic_turning_sim_paper.py:457): per-link forces [N*L,3] at

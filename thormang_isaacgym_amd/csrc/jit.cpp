@@ -35,7 +35,7 @@ namespace tg {
 namespace {
 
 enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, K_ID, K_CENTROIDAL, K_CID, K_SCAN,
-       K_IMU, NK };
+       K_IMU, K_RAY, NK };
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, false, tg::NoPost>",
@@ -51,6 +51,7 @@ const char *const KERNEL_EXPR[NK] = {
     "tg::contact_inverse_dynamics_kernel<TgJitModel>",
     "tg::height_scan_kernel<TgJitModel>",
     "tg::imu_kernel<TgJitModel>",
+    "tg::ray_cast_kernel<TgJitModel>",
 };
 // the per-model launch figures the host needs, read back from the module
 // (tgjit_meta, same order)
@@ -159,7 +160,7 @@ int compile(const std::string &src, const std::string &incdir, JitCode &out, std
     return 0;
 }
 
-// cache file: "TGJIT9\n", one lowered name per line, then the code object
+// cache file: "TGJIT10\n", one lowered name per line, then the code object
 bool cache_load(const std::string &path, JitCode &out) {
     std::string s;
     if (!read_file(path, s)) return false;
@@ -172,7 +173,7 @@ bool cache_load(const std::string &path, JitCode &out) {
         return true;
     };
     std::string magic;
-    if (!line(magic) || magic != "TGJIT9") return false;
+    if (!line(magic) || magic != "TGJIT10") return false;
     for (int k = 0; k < NK; ++k)
         if (!line(out.names[k]) || out.names[k].empty()) return false;
     if (pos >= s.size()) return false;
@@ -185,7 +186,7 @@ void cache_store(const std::string &path, const JitCode &c) {
     {
         std::ofstream f(tmp, std::ios::binary);
         if (!f) return;
-        f << "TGJIT9\n";
+        f << "TGJIT10\n";
         for (int k = 0; k < NK; ++k) f << c.names[k] << "\n";
         f.write(c.code.data(), (std::streamsize)c.code.size());
         if (!f) return;
@@ -400,6 +401,15 @@ int jit_launch_imu(uint64_t hash, const float *root, const float *dof, int n, co
     ImuArgs aa = ia;
     void *args[] = {&root, &dof, &n, &aa, &bias, &reset, &history, &out};
     return launch(L->f[K_IMU], (unsigned)n, 64, 0, stream, args);
+}
+
+int jit_launch_ray_cast(uint64_t hash, const float *root, const float *dof, const float *rays, int n,
+                        const RayArgs &ra, float *dist, float *normals, hipStream_t stream) {
+    JitLoaded *L = find(hash);
+    if (!L) return TG_ERR_MODEL;
+    RayArgs aa = ra;
+    void *args[] = {&root, &dof, &rays, &n, &aa, &dist, &normals};
+    return launch(L->f[K_RAY], (unsigned)n * (unsigned)ray_chunks(ra), 64, 0, stream, args);
 }
 
 }  // namespace tg

@@ -62,6 +62,27 @@ struct ImuArgs {
     uint32_t k0, k1, c_lo, c_hi;
 };
 
+// what a tg_ray_cast call hands ray_cast_kernel by value: the frames, the counts, the alignment, the bound on the ray
+// parameter and the sim's heightfield at the time of the call under the member names of StepArgs (hf null: no
+// terrain); hf_zcap: no vertex of the terrain is higher (tg_set_heightfield forms it on the host, with a margin), so
+// that a ray above it need not be walked
+struct RayArgs {
+    tg_contact_frame f[TG_RAY_MAX_FRAMES];
+    int F, R, align;
+    float max_range;
+    const float *hf;
+    int hf_rows, hf_cols;
+    float hf_hs, hf_vs, hf_ox, hf_oy, hf_zcap;
+};
+// samples (frame, ray) of one env that a block of ray_cast_kernel takes, and the blocks per env of a call.  256 was
+// the fastest of 64, 256 and 1024; a developer build with -DTG_RAY_CHUNK=... measures another size on
+// the compiled-in models (run-time models are compiled with the default and do not fit such a build)
+#ifndef TG_RAY_CHUNK
+#define TG_RAY_CHUNK 256
+#endif
+constexpr int RAY_CHUNK = TG_RAY_CHUNK;
+__host__ __device__ inline int ray_chunks(const RayArgs &a) { return (a.F * a.R + RAY_CHUNK - 1) / RAY_CHUNK; }
+
 // the sensors of tg_set_force_sensor_tensor as the step kernel takes them by value (step_par.h NoPostFS): the
 // frames as registered, their count and the axes of the output (TG_ENV_SPACE / TG_LOCAL_SPACE)
 struct FsFrames {
@@ -273,6 +294,10 @@ int launch_height_scan(uint64_t hash, const float *root, const float *dof, const
 // bias [N, S, 6] and reset [N]) (imu_kernel; tgsim.h tg_imu)
 int launch_imu(uint64_t hash, const float *root, const float *dof, int n, const ImuArgs &ia, const float *bias,
                const int64_t *reset, float *history, float *out, hipStream_t stream);
+// ray distances [N, F, R] and hit normals [N, F, R, 3], each optional, of the pattern rays [R, 6] cast from F link
+// frames (ray_cast_kernel; tgsim.h tg_ray_cast)
+int launch_ray_cast(uint64_t hash, const float *root, const float *dof, const float *rays, int n, const RayArgs &ra,
+                    float *dist, float *normals, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
@@ -322,6 +347,8 @@ int jit_launch_height_scan(uint64_t hash, const float *root, const float *dof, c
                            const ScanArgs &sa, float *heights, float *normals, hipStream_t stream);
 int jit_launch_imu(uint64_t hash, const float *root, const float *dof, int n, const ImuArgs &ia, const float *bias,
                    const int64_t *reset, float *history, float *out, hipStream_t stream);
+int jit_launch_ray_cast(uint64_t hash, const float *root, const float *dof, const float *rays, int n,
+                        const RayArgs &ra, float *dist, float *normals, hipStream_t stream);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

@@ -6,6 +6,8 @@
 // through tg_last_error().  All work is stream-ordered on the sim's stream.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -91,6 +93,7 @@ struct tg_sim {
     float *hf = nullptr;
     int hf_rows = 0, hf_cols = 0;
     float hf_hs = 0.f, hf_vs = 0.f, hf_ox = 0.f, hf_oy = 0.f, hf_mu = 0.f;
+    float hf_zcap = 0.f;   // no vertex is higher than this (formed on the host; tg_ray_cast skips the air above it)
     std::vector<void *> allocs;
     // kernel timing (tg_set_kernel_timing): event pairs recorded, not yet read
     bool walk_unfused = false;   // tg_walk_step: separate post-physics launch (TG_WALK_UNFUSED=1)
@@ -514,6 +517,18 @@ int tg_set_heightfield(tg_sim *s, const float *heights, int32_t rows, int32_t co
     s->hf_ox = origin_x;
     s->hf_oy = origin_y;
     s->hf_mu = friction;
+    // the highest vertex, with a margin far above fp32 rounding so that a ray clipped to z <= hf_zcap loses no hit;
+    // FLT_MAX (no clipping) when a sample is not finite
+    float zmax = -FLT_MAX;
+    for (size_t k = 0; k < (size_t)rows * cols; ++k) {
+        const float z = vertical_scale * heights[k];
+        if (!std::isfinite(z)) {
+            zmax = FLT_MAX;
+            break;
+        }
+        zmax = std::max(zmax, z);
+    }
+    s->hf_zcap = zmax < FLT_MAX ? zmax + 1e-4f * std::max(1.f, std::fabs(zmax)) : FLT_MAX;
     return TG_OK;
 }
 
@@ -1003,6 +1018,55 @@ int tg_imu(tg_sim *s, const tg_contact_frame *sensors, int32_t num_sensors, cons
     DeviceGuard dg(s->device);
     win_touch(s);
     if (int rc = tg::launch_imu(s->hash, s->root, s->dof, (int)s->N, ia, bias, reset, history, out, s->stream))
+        return fail(rc, "%s: launch failed", fn);
+    return TG_OK;
+}
+
+int tg_ray_cast(tg_sim *s, const tg_contact_frame *frames, int32_t num_frames, const float *rays, int32_t num_rays,
+                const tg_ray_params *params, float *dist, float *normals) {
+    const char *fn = "tg_ray_cast";
+    // everything that can be judged without the sim first, then the sim, then the links against its model
+    if (!frames) return fail(TG_ERR_ARG, "%s: null frames", fn);
+    if (!rays) return fail(TG_ERR_ARG, "%s: null rays", fn);
+    if (!params) return fail(TG_ERR_ARG, "%s: null params", fn);
+    if (!dist && !normals) return fail(TG_ERR_ARG, "%s: dist and normals are both null", fn);
+    if (num_frames < 1 || num_frames > TG_RAY_MAX_FRAMES)
+        return fail(TG_ERR_ARG, "%s: num_frames %d outside 1..%d", fn, num_frames, TG_RAY_MAX_FRAMES);
+    if (num_rays < 1 || num_rays > TG_RAY_MAX_RAYS)
+        return fail(TG_ERR_ARG, "%s: num_rays %d outside 1..%d", fn, num_rays, TG_RAY_MAX_RAYS);
+    tg::RayArgs ra{};
+    for (int k = 0; k < num_frames; ++k) {
+        if (frames[k].link < 0) return fail(TG_ERR_ARG, "%s: frame %d: link %d is negative", fn, k, frames[k].link);
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(frames[k].offset[i]))
+                return fail(TG_ERR_ARG, "%s: frame %d: offset[%d] is not finite", fn, k, i);
+        ra.f[k] = frames[k];
+    }
+    const tg_ray_params &p = *params;
+    if (p.align != TG_RAY_LINK && p.align != TG_RAY_YAW && p.align != TG_RAY_WORLD)
+        return fail(TG_ERR_ARG, "%s: align %d is none of TG_RAY_LINK, TG_RAY_YAW, TG_RAY_WORLD", fn, p.align);
+    if (!(std::isfinite(p.max_range) && p.max_range > 0.f))
+        return fail(TG_ERR_ARG, "%s: max_range %g is not a finite number > 0", fn, (double)p.max_range);
+    if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
+    for (int k = 0; k < num_frames; ++k)
+        if (frames[k].link >= s->L)
+            return fail(TG_ERR_ARG, "%s: frame %d: link %d outside [0, %d)", fn, k, frames[k].link, s->L);
+    ra.F = num_frames;
+    ra.R = num_rays;
+    ra.align = p.align;
+    ra.max_range = p.max_range;
+    // the heightfield of this moment (step_args hands the step kernel the same members)
+    ra.hf = s->hf_rows > 0 ? s->hf : nullptr;
+    ra.hf_rows = s->hf_rows;
+    ra.hf_cols = s->hf_cols;
+    ra.hf_hs = s->hf_hs;
+    ra.hf_vs = s->hf_vs;
+    ra.hf_ox = s->hf_ox;
+    ra.hf_oy = s->hf_oy;
+    ra.hf_zcap = s->hf_zcap;
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_ray_cast(s->hash, s->root, s->dof, rays, (int)s->N, ra, dist, normals, s->stream))
         return fail(rc, "%s: launch failed", fn);
     return TG_OK;
 }

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 import os
 from collections import namedtuple
 
@@ -140,6 +141,7 @@ def _ptr(t: torch.Tensor | None):
 Centroidal = namedtuple("Centroidal", ["state", "matrix", "bias"])   # what Sim.centroidal returns
 ContactDynamics = namedtuple("ContactDynamics", ["tau", "wrench"])   # what Sim.contact_inverse_dynamics returns
 HeightScan = namedtuple("HeightScan", ["heights", "normals"])   # what Sim.height_scan returns
+RayCast = namedtuple("RayCast", ["dist", "normals"])   # what Sim.ray_cast returns
 # what Sim.imu returns: views of raw [N, S, 20]
 Imu = namedtuple("Imu", ["quat", "gravity", "lin_vel", "ang_vel", "lin_acc", "ang_acc", "valid", "raw"])
 
@@ -932,6 +934,110 @@ class Sim:
             views = self._imu_views = Imu(raw[..., 0:4], raw[..., 4:7], raw[..., 7:10], raw[..., 10:13],
                                           raw[..., 13:16], raw[..., 16:19], raw[..., 19], raw)
         return views
+
+    def lidar_rays(self, azimuths, elevations) -> torch.Tensor:
+        """The pattern ``[len(elevations) * len(azimuths), 6]`` of ``ray_cast``
+        for a lidar: unit directions ``(cos e cos a, cos e sin a, sin e)``
+        (radians; x forward, y left, z up), starts zero, elevation-major -- the
+        azimuth varies fastest, one ring after the other.  float32 on the
+        sim's device; with unit directions ``dist`` is the range."""
+        a = torch.as_tensor(azimuths, dtype=torch.float64).reshape(-1)
+        e = torch.as_tensor(elevations, dtype=torch.float64).reshape(-1)
+        ee, aa = torch.meshgrid(e, a, indexing="ij")
+        d = torch.stack([torch.cos(ee) * torch.cos(aa), torch.cos(ee) * torch.sin(aa), torch.sin(ee)], dim=-1)
+        rays = torch.cat([torch.zeros_like(d), d], dim=-1).reshape(-1, 6)
+        return rays.to(torch.float32).contiguous().to(self.device)
+
+    def pinhole_rays(self, width: int, height: int, hfov: float) -> torch.Tensor:
+        """The pattern ``[height * width, 6]`` of ``ray_cast`` for a pinhole
+        depth camera looking along x (y left, z up) with the horizontal field
+        of view ``hfov`` (radians) and square pixels: row-major from the
+        top-left pixel, pixel (r, c) has the direction ``(1, T (1 - 2 (c + 1/2)
+        / W), T (H / W) (1 - 2 (r + 1/2) / H))``, ``T = tan(hfov / 2)``, starts
+        zero.  The directions are scaled to ``d.x = 1``, not to unit length, so
+        that ``dist`` is the depth along the optical axis and ``max_range``
+        bounds the depth.  float32 on the sim's device."""
+        W, H = int(width), int(height)
+        if W < 1 or H < 1 or not 0.0 < float(hfov) < math.pi:
+            raise ValueError("pinhole_rays needs width, height >= 1 and 0 < hfov < pi")
+        T = math.tan(0.5 * float(hfov))
+        c = torch.arange(W, dtype=torch.float64)
+        r = torch.arange(H, dtype=torch.float64)
+        rr, cc = torch.meshgrid(r, c, indexing="ij")
+        d = torch.stack([torch.ones_like(cc), T * (1.0 - 2.0 * (cc + 0.5) / W),
+                         T * (H / W) * (1.0 - 2.0 * (rr + 0.5) / H)], dim=-1)
+        rays = torch.cat([torch.zeros_like(d), d], dim=-1).reshape(-1, 6)
+        return rays.to(torch.float32).contiguous().to(self.device)
+
+    def ray_cast(self, frames, rays: torch.Tensor, align: str = "link", max_range: float = 20.0,
+                 normals: bool = False, out: torch.Tensor | None = None,
+                 out_normals: torch.Tensor | None = None) -> "RayCast":
+        """Lidar and depth-camera ranges in one kernel launch (tgsim.h
+        tg_ray_cast), from the current state and the sim's heightfield, on the
+        sim's stream.  ``frames``: 1..8 ``contact_frame`` (a link, by name or
+        index, stands for its origin); ``rays`` [R, 6] float32 on the sim's
+        device (``lidar_rays``, ``pinhole_rays``), a start offset and a
+        direction per ray, one pattern for every env and frame, R <= 4096.  The
+        pattern is given in the link's own axes (``align="link"``), in axes
+        turned by the link's heading only (``"yaw"``, ``height_scan``'s rule)
+        or in world axes (``"world"``).  Ray k of frame f is ``x(t) = p_f + A
+        s_k + t A d_k``; it is cast against the ground the contacts feel -- the
+        solid under the heightfield's triangles and the z <= 0 half-space.
+        Returns ``RayCast(dist, normals)``: ``dist`` [N, F, R], the smallest
+        ``t`` in ``[0, max_range]`` at which the ray is in the ground
+        (directions are not normalised: the range for unit directions, the
+        depth for ``pinhole_rays``), and exactly ``max_range`` on a miss; with
+        ``normals`` the unit normal of what was hit [N, F, R, 3] (zero on a
+        miss), else None.  ``out`` and ``out_normals`` are checked and, for a
+        requested part, written and returned as given; without them the tensors
+        are owned by the sim and overwritten by the next call with as many
+        frames and rays."""
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        def own(key, shape):
+            buf = getattr(self, "_ray_out", None)
+            if buf is None:
+                buf = self._ray_out = {}
+            if (key, shape) not in buf:
+                buf[key, shape] = torch.zeros(*shape, dtype=torch.float32, device=self.device)
+            return buf[key, shape]
+
+        aligns = {"link": abi.TG_RAY_LINK, "yaw": abi.TG_RAY_YAW, "world": abi.TG_RAY_WORLD}
+        if align not in aligns:
+            raise ValueError(f"align must be one of {sorted(aligns)}, got {align!r}")
+        max_range = float(max_range)
+        if not (math.isfinite(max_range) and max_range > 0.0):
+            raise ValueError(f"max_range must be a finite number > 0, got {max_range}")
+        frames = [c if isinstance(c, abi.tg_contact_frame) else self.contact_frame(c) for c in frames]
+        F = len(frames)
+        if not 1 <= F <= abi.TG_RAY_MAX_FRAMES:
+            raise ValueError(f"ray_cast takes 1..{abi.TG_RAY_MAX_FRAMES} frames, got {F}")
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must be a [R, 6] tensor")
+        R = int(rays.shape[0])
+        if not 1 <= R <= abi.TG_RAY_MAX_RAYS:
+            raise ValueError(f"ray_cast takes 1..{abi.TG_RAY_MAX_RAYS} rays, got {R}")
+        checked(rays, (R, 6), "rays")
+        N = self.num_envs
+        shapes = {"out": (N, F, R), "out_normals": (N, F, R, 3)}
+        given = {"out": out, "out_normals": out_normals}
+        for key, t in given.items():
+            if t is not None:
+                checked(t, shapes[key], key)
+        dt, nt = ((given[key] if given[key] is not None else own(key, shapes[key])) if asked else None
+                  for key, asked in (("out", True), ("out_normals", normals)))
+        rp = abi.tg_ray_params()
+        rp.align, rp.max_range = aligns[align], max_range
+        arr = (abi.tg_contact_frame * F)(*frames)
+        check(lib().tg_ray_cast(self._h, arr, F, _ptr(rays), R, C.byref(rp), _ptr(dt), _ptr(nt)), "ray_cast")
+        self._keep_rays = rays   # read on the sim stream; held until the next call
+        return RayCast(dt, nt)
 
     @property
     def contact_link_indices(self) -> list:

@@ -318,6 +318,12 @@ class VecTask(Env):
         return self.sim.height_scan(frames, points, surface=surface, align=align, normals=normals, relative=relative,
                                     out=out, out_normals=out_normals)
 
+    def ray_cast(self, frames, rays, align="link", max_range=20.0, normals=False, out=None, out_normals=None):
+        """Ray distances [N, F, R] and optionally the hit normals [N, F, R, 3] of the pattern ``rays`` [R, 6] cast
+        from the link frames ``frames`` against the ground, in one kernel (Sim.ray_cast)."""
+        return self.sim.ray_cast(frames, rays, align=align, max_range=max_range, normals=normals, out=out,
+                                 out_normals=out_normals)
+
     def imu(self, sensors, history=None, dt=None, reset=None, bias=None, gyro_noise=0.0, accel_noise=0.0, seed=0,
             counter=0, out=None):
         """IMU readings [N, S, 20] at the link frames ``sensors`` -- quaternion, projected gravity, body-frame

@@ -33,6 +33,18 @@ heading, on the surface the contacts feel (tgsim.h tg_height_scan), of the
 state the step returns with: one extra kernel launch per step, zeros on the
 flat ground.  Observation, reward and reset do not read it, and the step itself
 is unchanged.
+
+``env.enableDepthCamera: true`` (optional, default false) adds
+``extras["depth"]`` [N,24,32] after every step -- a depth image of the ground
+ahead, 32 x 24 pixels of a pinhole camera with an 87 degree horizontal field of
+view at ``realsense_link``, rays cast against the terrain solid and the z = 0
+plane (tgsim.h tg_ray_cast) from the state the step returns with; a pixel is the
+depth along the optical axis in metres, 8.0 where nothing is hit within 8 m.
+In the URDF the model was built from ``realsense_fixed`` has rpy 0 and the
+link's axes at the zero pose are the body's (x forward, y left, z up): x is the
+optical axis, the pattern of ``Sim.pinhole_rays`` is used as it is
+(``align="link"``), and no fixed rotation is baked in.  One extra kernel launch
+per step; observation, reward and reset do not read it.
 """
 from __future__ import annotations
 
@@ -144,6 +156,13 @@ class Gogoro(VecTask):
                                                     0.1 * torch.tensor(self.HEIGHT_SCAN_Y, dtype=torch.float32))
             self._scan_frames = [self.sim.contact_frame(0)]
             self.measured_heights = torch.zeros(self.n_envs, 1, self.height_points.shape[0], device=self.sim.device)
+        # env.enableDepthCamera: a 32 x 24 depth image of the ground ahead from realsense_link (tg_ray_cast);
+        # observation, reward and reset do not use it
+        self.depth = None
+        if bool(self.cfg["env"].get("enableDepthCamera", False)):
+            self.depth_rays = self.sim.pinhole_rays(self.DEPTH_WIDTH, self.DEPTH_HEIGHT, self.DEPTH_HFOV)
+            self._depth_frames = [self.sim.contact_frame("realsense_link")]
+            self.depth = torch.zeros(self.n_envs, 1, self.DEPTH_WIDTH * self.DEPTH_HEIGHT, device=self.sim.device)
         self.reset_idx(torch.arange(0, self.n_envs, device=self.device).type(torch.long))
 
     # ------------------------------------------------------------ creation
@@ -169,6 +188,12 @@ class Gogoro(VecTask):
     #: (in tenths of a metre; scaled in float32 as the reference does)
     HEIGHT_SCAN_X = (-8, -7, -6, -5, -4, -3, -2, 2, 3, 4, 5, 6, 7, 8)
     HEIGHT_SCAN_Y = (-5, -4, -3, -2, -1, 1, 2, 3, 4, 5)
+
+    #: the depth camera of env.enableDepthCamera at realsense_link: pixels, horizontal field of view (radians, the
+    #: 87 degrees of the sensor's depth stream) and the bound on the depth in metres
+    DEPTH_WIDTH, DEPTH_HEIGHT = 32, 24
+    DEPTH_HFOV = 87.0 * np.pi / 180.0
+    DEPTH_MAX = 8.0
 
     def _create_ground_plane(self):
         """The Perlin terrain beside the z = 0 plane (gogoro_new.py:164-181):
@@ -268,6 +293,10 @@ class Gogoro(VecTask):
             self.height_scan(self._scan_frames, self.height_points, surface="surface", align="yaw",
                              out=self.measured_heights)
             self.extras["measured_heights"] = self.measured_heights[:, 0].to(self.rl_device)
+        # extras["depth"] [N, 24, 32]: the depth image of the state the step returns with (env.enableDepthCamera)
+        if getattr(self, "depth", None) is not None:
+            self.ray_cast(self._depth_frames, self.depth_rays, align="link", max_range=self.DEPTH_MAX, out=self.depth)
+            self.extras["depth"] = self.depth.view(self.n_envs, self.DEPTH_HEIGHT, self.DEPTH_WIDTH).to(self.rl_device)
 
     def compute_obs_rwd(self):
         """Fused into post_physics_step (tg_gogoro_post_physics); kept for API parity."""
