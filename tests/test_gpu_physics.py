@@ -342,6 +342,137 @@ def abi_hash(m):
     return abi.ModelDesc(m).hash
 
 
+# max |compiled-in - run-time| per output of test_gpu_runtime_on_demand_kernels_equal_compiled, measured on the
+# MI355X at the commit before the on-demand kernels' launchers were folded into one dispatch
+ON_DEMAND_MEASURED = {
+    "body_force": 0.0, "rigid_body_state": 0.0, "jacobian": 0.0, "mass_matrix": 0.0,
+    "ik_targets": 0.0, "ik_dq": 0.0, "ik_err": 0.0, "osc_efforts": 0.0, "osc_tau": 0.0, "osc_err": 0.0,
+    "id_efforts": 0.0, "id_tau": 0.0, "cid_efforts": 0.0, "cid_tau": 0.0, "cid_wrench": 0.0,
+    "centroidal_state": 2.0 ** -21, "centroidal_matrix": 2.0 ** -21, "centroidal_bias": 0.0,   # 4.8e-7
+    "scan_heights": 0.0, "scan_normals": 0.0, "imu_history": 0.0, "imu_raw": 0.0,
+    "ray_dist": 0.0, "ray_normals": 0.0,
+}
+
+
+def test_gpu_runtime_on_demand_kernels_equal_compiled():
+    """Every on-demand kernel (the list in csrc/tg_kernels.h) on the run-time
+    (hipRTC) specialisation of Thormang, registered under another hash,
+    against the compiled-in instantiation on identical inputs, each output on
+    its own.  The two differ in how the launch is formed -- hipLaunchKernelGGL
+    with typed arguments against hipModuleLaunchKernel with an array of
+    pointers -- and, the source and the numerics flags being the same, in
+    instruction scheduling at the most: anything beyond rounding is an
+    argument in the wrong place, and those give errors of order one.  The
+    bound per output is twice the figure of ON_DEMAND_MEASURED, at least one
+    fp32 ulp of the output's largest magnitude.  Measured before the change:
+    0 for 22 of the 24 outputs, 4.8e-7 (2^-21, an eighth of an ulp of the
+    largest entry) for the centroidal state and momentum matrix.
+
+    3 envs are no multiple of COMPOSE_WPB = 8 (rb_force_kernel's rounded
+    grid); 2 frames x 129 rays = 258 samples need two blocks of
+    ray_cast_kernel per env (RAY_CHUNK = 256).  rb_force_kernel runs as the
+    launch of its own only when no env can be dirty, hence the simulate
+    before the forces are applied, and the check of the launch counter."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs the MI355X")
+    from tests.call_sequences import launch_stats, since
+    from thormang_isaacgym_amd.sim import Sim, load_model
+    m = load_model("thormang")
+    n, D, L = 3, m.num_dof, m.num_bodies
+    desc, sp, root, dof, props, pt, vt = pm.sim(m, n=n, dt=1 / 60, substeps=2)
+    rs = np.random.default_rng(12)
+    root[:, :2] = rs.uniform(-0.3, 0.3, (n, 2))
+    root[:, 2] = 1.2
+    q = np.array([0.0, 0.0, 0.0, 1.0]) + rs.normal(0, 1, (n, 4)) * [0.1, 0.1, 0.3, 0.0]
+    root[:, 3:7] = q / np.linalg.norm(q, axis=1, keepdims=True)
+    root[:, 7:13] = rs.normal(0, 0.3, (n, 6))
+    dof[:, 0] = rs.uniform(-0.3, 0.3, n * D)
+    dof[:, 1] = rs.normal(0, 0.5, n * D)
+    heights = rs.uniform(0.0, 3.0, (6, 5)).astype(np.float32)
+
+    def cuda(a):
+        return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+
+    mass_scale = cuda(rs.uniform(0.9, 1.1, (n, L)))
+    forces, torques = cuda(rs.normal(0, 20.0, (n * L, 3))), cuda(rs.normal(0, 2.0, (n * L, 3)))
+    goal_pos, goal_quat = cuda(rs.uniform(-0.5, 0.5, (n, 2, 3))), rs.normal(0, 1, (n, 2, 4))
+    goal_quat = cuda(goal_quat / np.linalg.norm(goal_quat, axis=2, keepdims=True))
+    q_rest, accel = cuda(rs.uniform(-0.2, 0.2, (n, D))), cuda(rs.normal(0, 1.0, (n, 6 + D)))
+    share = cuda(rs.uniform(0.5, 1.5, (n, 2)))
+    imu_bias = cuda(rs.normal(0, 0.05, (n, 2, 6)))
+    imu_reset = torch.tensor([0, 1, 0], dtype=torch.int64, device="cuda:0")
+    efforts0 = cuda(rs.uniform(-0.1, 0.1, (n, D)))
+
+    sims, outs = [], []
+    for jh in (None, 0x7E57_0000_0000_0000 | (abi_hash(m) & 0xFFFF_FFFF)):
+        s = Sim(m, sp, n, "cuda:0", jit_hash=jh)
+        s.root_state.copy_(torch.from_numpy(root))
+        s.dof_state.copy_(torch.from_numpy(dof))
+        s.dof_props.copy_(torch.from_numpy(props))
+        s.env_dirty.fill_(1)
+        s.set_body_mass_scale_indexed(mass_scale, s.all_ids)
+        s.set_heightfield(heights, 0.5, 0.1, -1.5, -1.25)
+        sims.append(s)
+    assert not sims[0].jit and sims[1].jit
+
+    # rb_force_kernel: the launch of its own of a simulate that composes nothing
+    for s in sims:
+        s.simulate()
+        before = launch_stats(s)
+        assert s.apply_rigid_body_force_tensors(forces, torques, Sim.LOCAL_SPACE)
+        s.simulate()
+        assert since(s, before)["rb_launch"] == 1
+        outs.append({"body_force": s.body_force.clone()})
+    # the eleven others read the state alone: the same one for both sims
+    sims[1].root_state.copy_(sims[0].root_state)
+    sims[1].dof_state.copy_(sims[0].dof_state)
+
+    for s, o in zip(sims, outs):
+        o["rigid_body_state"] = s.acquire_rigid_body_state_tensor()
+        s.refresh_rigid_body_state_tensor()
+        o["jacobian"] = s.acquire_jacobian_tensor()
+        s.refresh_jacobian_tensors()
+        o["mass_matrix"] = s.acquire_mass_matrix_tensor()
+        s.refresh_mass_matrix_tensors()
+        chains = [s.ik_chain("l_arm_end_link"), s.ik_chain("r_leg_foot_link", num_dofs=6, offset=(0.05, -0.02, -0.03))]
+        o["ik_targets"] = torch.zeros(n, D, device="cuda:0")
+        o["ik_dq"], o["ik_err"] = s.solve_ik(chains, goal_pos, goal_quat, damping=0.3, targets=o["ik_targets"],
+                                             return_error=True)
+        o["osc_efforts"] = efforts0.clone()
+        o["osc_tau"], o["osc_err"] = s.solve_osc(chains, goal_pos, goal_quat, q_rest=q_rest, efforts=o["osc_efforts"],
+                                                 return_error=True)
+        o["id_efforts"] = efforts0.clone()
+        o["id_tau"] = s.inverse_dynamics(accel=accel, dofs=[1, 5, D - 1], efforts=o["id_efforts"], accumulate=True)
+        feet = [s.contact_frame("l_leg_foot_link", (0.03, 0.01, -0.04)),
+                s.contact_frame("r_leg_foot_link", (0.02, -0.015, -0.04))]
+        o["cid_efforts"] = efforts0.clone()
+        o["cid_tau"], o["cid_wrench"] = s.contact_inverse_dynamics(feet, share=share, accel=accel, moment_arm=0.07,
+                                                                   efforts=o["cid_efforts"])
+        o["centroidal_state"], o["centroidal_matrix"], o["centroidal_bias"] = s.centroidal(matrix=True, bias=True)
+        o["scan_heights"], o["scan_normals"] = s.height_scan(feet, s.scan_grid([-0.2, 0.0, 0.3], [-0.1, 0.15]),
+                                                             normals=True)
+        o["imu_history"] = s.imu_history(2)
+        s.imu(feet, history=o["imu_history"])
+        o["imu_raw"] = s.imu(feet, history=o["imu_history"], reset=imu_reset, bias=imu_bias, gyro_noise=0.01,
+                             accel_noise=0.02, seed=5, counter=9).raw
+        rays = s.lidar_rays(np.deg2rad(360.0 / 43 * np.arange(43)), np.deg2rad([-60.0, -35.0, -10.0]))
+        assert len(feet) * rays.shape[0] == 258
+        o["ray_dist"], o["ray_normals"] = s.ray_cast(feet, rays, align="yaw", max_range=5.0, normals=True)
+    torch.cuda.synchronize()
+
+    figures, bounds = {}, {}
+    for k, a in outs[0].items():
+        assert torch.isfinite(a).all() and torch.isfinite(outs[1][k]).all(), k
+        top = float(a.abs().max())
+        assert top > 0.0, k                     # (an output nothing was written to would compare equal)
+        figures[k] = float((a - outs[1][k]).abs().max())
+        bounds[k] = max(2.0 * ON_DEMAND_MEASURED.get(k, 0.0), float(np.spacing(np.float32(top))))
+    print({"on_demand_max_abs_diff": figures, "bounds": bounds})
+    assert set(ON_DEMAND_MEASURED) <= set(figures)
+    for k in figures:
+        assert figures[k] <= bounds[k], (k, figures[k], bounds[k])
+
+
 def test_gpu_native_urdf_load_through_the_c_abi_alone():
     """gym.load_asset without the Python host: tg_model_load (csrc/model_load.cpp
     parses the URDF, builds the descriptor and the specialisation's traits and

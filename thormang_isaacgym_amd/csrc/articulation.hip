@@ -123,122 +123,114 @@ ModelInfo model_info(uint64_t hash) {
     return i;
 }
 
-// the on-demand kernels: a compiled-in model's instantiation, else the
-// run-time model's (jit.cpp)
 template <class... P, class... A>
-static int run(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t stream, A... args) {
+static int run(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t stream, const A &...args) {
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
     return hipGetLastError() == hipSuccess ? 0 : TG_ERR_HIP;
 }
 
-int launch_body_states(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
+// the on-demand kernels (the list in tg_kernels.h): OnDemand<K, M>::kernel is kernel K's instantiation for model M
+template <int K, class M> struct OnDemand;
+#define TG_OD_KERNEL(ID, KERNEL) \
+    template <class M> struct OnDemand<OD_##ID, M> { static constexpr auto kernel = &KERNEL<M>; };
+TG_FOR_EACH_ON_DEMAND(TG_OD_KERNEL)
+#undef TG_OD_KERNEL
+// (any compiled-in model: a kernel's parameter list does not depend on the model)
+template <class M, class...> using FirstOf = M;
+#define TG_MODEL_COMMA(MODEL) MODEL,
+using AnyModel = FirstOf<TG_FOR_EACH_MODEL(TG_MODEL_COMMA) void>;
+#undef TG_MODEL_COMMA
+template <class T> struct AsIs { using type = T; };   // (keeps a parameter out of template argument deduction)
+
+// Launches kernel K with the arguments p: a compiled-in model's instantiation, else the run-time model's (jit.cpp)
+// with the same grid, block and arguments.  P... are the kernel's own parameter types, so the array of pointers that
+// hipModuleLaunchKernel reads has the kernel's count, order and types by construction, and a by-value struct is
+// copied once, into p.
+template <int K, class... P>
+static int on_demand_as(void (*)(P...), uint64_t hash, unsigned grid, unsigned block, hipStream_t stream,
+                        typename AsIs<P>::type... p) {
     int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(body_state_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, n, out);
-    }) ? rc : jit_launch_body_states(hash, root, dof, n, out, stream);
+    if (with_model(hash, [&](auto m) {
+            constexpr void (*kernel)(P...) = OnDemand<K, decltype(m)>::kernel;   // (every model: the same parameters)
+            rc = run(kernel, dim3(grid), dim3(block), stream, p...);
+        }))
+        return rc;
+    void *args[] = {(void *)&p...};
+    return jit_launch(hash, K, grid, block, stream, args);
+}
+// a call's arguments a, converted to the parameter types of kernel K: a wrong count or type does not compile
+template <int K, class... A>
+static int on_demand(uint64_t hash, unsigned grid, unsigned block, hipStream_t stream, const A &...a) {
+    return on_demand_as<K>(OnDemand<K, AnyModel>::kernel, hash, grid, block, stream, a...);
+}
+
+int launch_body_states(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
+    return on_demand<OD_BODY>(hash, n, 64, stream, root, dof, n, out);
 }
 
 int launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(jacobian_kernel<decltype(m)>, dim3(n), dim3(JAC_THREADS), stream, root, dof, n, out);
-    }) ? rc : jit_launch_jacobians(hash, root, dof, n, out, stream);
+    return on_demand<OD_JAC>(hash, n, JAC_THREADS, stream, root, dof, n, out);
 }
 
 int launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                          const float *props, int n, float *out, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(mass_matrix_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, props, n, out);
-    }) ? rc : jit_launch_mass_matrices(hash, root, dof, mass_scale, props, n, out, stream);
+    return on_demand<OD_MASS>(hash, n, 64, stream, root, dof, mass_scale, props, n, out);
 }
 
 int launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
                   const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
                   float *pos_targets, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(ik_dls_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, n, ch, K, goal_pos, goal_quat,
-                 lambda2, dq, err, pos_targets);
-    }) ? rc : jit_launch_ik_dls(hash, root, dof, n, ch, K, goal_pos, goal_quat, lambda2, dq, err, pos_targets, stream);
+    return on_demand<OD_IK>(hash, n, 64, stream, root, dof, n, ch, K, goal_pos, goal_quat, lambda2, dq, err,
+                            pos_targets);
 }
 
 int launch_osc(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props, int n,
                const IkChains &ch, int K, const float *goal_pos, const float *goal_quat, const float *q_rest,
                const OscGains &gains, float *tau, float *err, float *efforts, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(osc_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, props, n, ch, K, goal_pos,
-                 goal_quat, q_rest, gains, tau, err, efforts);
-    }) ? rc : jit_launch_osc(hash, root, dof, mass_scale, props, n, ch, K, goal_pos, goal_quat, q_rest, gains, tau,
-                             err, efforts, stream);
+    return on_demand<OD_OSC>(hash, n, 64, stream, root, dof, mass_scale, props, n, ch, K, goal_pos, goal_quat, q_rest,
+                             gains, tau, err, efforts);
 }
 
 int launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                             const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
                             float *efforts, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(inverse_dynamics_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, props, n, ia,
-                 accel, tau, efforts);
-    }) ? rc : jit_launch_inverse_dynamics(hash, root, dof, mass_scale, props, n, ia, accel, tau, efforts, stream);
+    return on_demand<OD_ID>(hash, n, 64, stream, root, dof, mass_scale, props, n, ia, accel, tau, efforts);
 }
 
 int launch_contact_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
                                     const float *props, int n, const IdArgs &ia, const CidArgs &ca, const float *share,
                                     const float *accel, float *tau, float *wrench, float *efforts,
                                     hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(contact_inverse_dynamics_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, props,
-                 n, ia, ca, share, accel, tau, wrench, efforts);
-    }) ? rc : jit_launch_contact_inverse_dynamics(hash, root, dof, mass_scale, props, n, ia, ca, share, accel, tau,
-                                                  wrench, efforts, stream);
+    return on_demand<OD_CID>(hash, n, 64, stream, root, dof, mass_scale, props, n, ia, ca, share, accel, tau, wrench,
+                             efforts);
 }
 
 int launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n, float *state,
                       float *matrix, float *bias, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(centroidal_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, mass_scale, n, state, matrix,
-                 bias);
-    }) ? rc : jit_launch_centroidal(hash, root, dof, mass_scale, n, state, matrix, bias, stream);
+    return on_demand<OD_CENTROIDAL>(hash, n, 64, stream, root, dof, mass_scale, n, state, matrix, bias);
 }
 
 int launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
                        const ScanArgs &sa, float *heights, float *normals, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(height_scan_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, points, n, sa, heights,
-                 normals);
-    }) ? rc : jit_launch_height_scan(hash, root, dof, points, n, sa, heights, normals, stream);
+    return on_demand<OD_SCAN>(hash, n, 64, stream, root, dof, points, n, sa, heights, normals);
 }
 
 int launch_imu(uint64_t hash, const float *root, const float *dof, int n, const ImuArgs &ia, const float *bias,
                const int64_t *reset, float *history, float *out, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(imu_kernel<decltype(m)>, dim3(n), dim3(64), stream, root, dof, n, ia, bias, reset, history, out);
-    }) ? rc : jit_launch_imu(hash, root, dof, n, ia, bias, reset, history, out, stream);
+    return on_demand<OD_IMU>(hash, n, 64, stream, root, dof, n, ia, bias, reset, history, out);
 }
 
 int launch_ray_cast(uint64_t hash, const float *root, const float *dof, const float *rays, int n, const RayArgs &ra,
                     float *dist, float *normals, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(ray_cast_kernel<decltype(m)>, dim3((unsigned)n * (unsigned)ray_chunks(ra)), dim3(64), stream, root,
-                 dof, rays, n, ra, dist, normals);
-    }) ? rc : jit_launch_ray_cast(hash, root, dof, rays, n, ra, dist, normals, stream);
+    return on_demand<OD_RAY>(hash, (unsigned)n * (unsigned)ray_chunks(ra), 64, stream, root, dof, rays, n, ra, dist,
+                             normals);
 }
 
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {
-    int rc = 0;
-    return with_model(hash, [&](auto m) {
-        rc = run(rb_force_kernel<decltype(m)>, dim3((n + COMPOSE_WPB - 1) / COMPOSE_WPB), dim3(64 * COMPOSE_WPB),
-                 stream, root, dof, comp, n, mass_scale, forces, torques, space, out, props);
-    }) ? rc : jit_launch_rb_forces(hash, root, dof, comp, n, mass_scale, forces, torques, space, out, props, stream);
+    return on_demand<OD_RBF>(hash, (n + COMPOSE_WPB - 1) / COMPOSE_WPB, 64 * COMPOSE_WPB, stream, root, dof, comp, n,
+                             mass_scale, forces, torques, space, out, props);
 }
 
 // the full compose of launch_compose (launch.h), shared-cache check included:

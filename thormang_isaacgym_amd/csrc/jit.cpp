@@ -9,7 +9,8 @@
 // text model/codegen.py emits), so a changed URDF needs no library rebuild.
 // The code object is cached on disk by (model hash, digest of the model text
 // and the kernel headers) and loaded per device with hipModuleLoadData; the
-// launchers in articulation.hip fall through to the jit_* functions below
+// launchers in articulation.hip fall through to jit_launch_step (the step)
+// and jit_launch (every on-demand kernel of the list in tg_kernels.h) below
 // when no compiled specialisation matches the hash.  The task epilogues
 // (tg_walk_step / tg_gogoro_step fusion) are not instantiated for run-time
 // models: those calls fall back to the separate task kernels.
@@ -34,25 +35,16 @@
 namespace tg {
 namespace {
 
-enum { K_COMPOSE, K_STEP, K_STEP_HF, K_BODY, K_RBF, K_JAC, K_MASS, K_IK, K_OSC, K_ID, K_CENTROIDAL, K_CID, K_SCAN,
-       K_IMU, K_RAY, NK };
+// the step's three kernels, then the on-demand kernels in the order of their list (tg_kernels.h): K_ON_DEMAND + OD_*
+enum { K_COMPOSE, K_STEP, K_STEP_HF, K_ON_DEMAND, NK = K_ON_DEMAND + OD_COUNT };
+#define TG_OD_EXPR(ID, KERNEL) "tg::" #KERNEL "<TgJitModel>",
 const char *const KERNEL_EXPR[NK] = {
     "tg::compose_kernel<TgJitModel>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, false, tg::NoPost>",
     "tg::step_par_kernel<TgJitModel, TgJitModel::EPB, true, tg::NoPost>",
-    "tg::body_state_kernel<TgJitModel>",
-    "tg::rb_force_kernel<TgJitModel>",
-    "tg::jacobian_kernel<TgJitModel>",
-    "tg::mass_matrix_kernel<TgJitModel>",
-    "tg::ik_dls_kernel<TgJitModel>",
-    "tg::osc_kernel<TgJitModel>",
-    "tg::inverse_dynamics_kernel<TgJitModel>",
-    "tg::centroidal_kernel<TgJitModel>",
-    "tg::contact_inverse_dynamics_kernel<TgJitModel>",
-    "tg::height_scan_kernel<TgJitModel>",
-    "tg::imu_kernel<TgJitModel>",
-    "tg::ray_cast_kernel<TgJitModel>",
+    TG_FOR_EACH_ON_DEMAND(TG_OD_EXPR)
 };
+#undef TG_OD_EXPR
 // the per-model launch figures the host needs, read back from the module
 // (tgjit_meta, same order)
 struct JitMeta {
@@ -300,116 +292,10 @@ int jit_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEve
     return 0;
 }
 
-int jit_launch_body_states(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
+int jit_launch(uint64_t hash, int kernel, unsigned grid, unsigned block, hipStream_t stream, void **args) {
     JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    void *args[] = {&root, &dof, &n, &out};
-    return launch(L->f[K_BODY], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
-                         const float *mass_scale, const float *forces, const float *torques, int space, float *out,
-                         const float *props, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    void *args[] = {&root, &dof, &comp, &n, &mass_scale, &forces, &torques, &space, &out, &props};
-    return launch(L->f[K_RBF], (unsigned)((n + COMPOSE_WPB - 1) / COMPOSE_WPB), 64 * COMPOSE_WPB, 0, stream,
-                  args);
-}
-
-int jit_launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    void *args[] = {&root, &dof, &n, &out};
-    return launch(L->f[K_JAC], (unsigned)n, JAC_THREADS, 0, stream, args);
-}
-
-int jit_launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
-                             const float *props, int n, float *out, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    void *args[] = {&root, &dof, &mass_scale, &props, &n, &out};
-    return launch(L->f[K_MASS], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
-                      const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
-                      float *pos_targets, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    IkChains cc = ch;
-    void *args[] = {&root, &dof, &n, &cc, &K, &goal_pos, &goal_quat, &lambda2, &dq, &err, &pos_targets};
-    return launch(L->f[K_IK], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_osc(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props,
-                   int n, const IkChains &ch, int K, const float *goal_pos, const float *goal_quat,
-                   const float *q_rest, const OscGains &gains, float *tau, float *err, float *efforts,
-                   hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    IkChains cc = ch;
-    OscGains gg = gains;
-    void *args[] = {&root, &dof, &mass_scale, &props, &n, &cc, &K, &goal_pos, &goal_quat, &q_rest, &gg, &tau, &err,
-                    &efforts};
-    return launch(L->f[K_OSC], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
-                                const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
-                                float *efforts, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    IdArgs aa = ia;
-    void *args[] = {&root, &dof, &mass_scale, &props, &n, &aa, &accel, &tau, &efforts};
-    return launch(L->f[K_ID], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_contact_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
-                                        const float *props, int n, const IdArgs &ia, const CidArgs &ca,
-                                        const float *share, const float *accel, float *tau, float *wrench,
-                                        float *efforts, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    IdArgs aa = ia;
-    CidArgs cc = ca;
-    void *args[] = {&root, &dof, &mass_scale, &props, &n, &aa, &cc, &share, &accel, &tau, &wrench, &efforts};
-    return launch(L->f[K_CID], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n,
-                          float *state, float *matrix, float *bias, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    void *args[] = {&root, &dof, &mass_scale, &n, &state, &matrix, &bias};
-    return launch(L->f[K_CENTROIDAL], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
-                           const ScanArgs &sa, float *heights, float *normals, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    ScanArgs aa = sa;
-    void *args[] = {&root, &dof, &points, &n, &aa, &heights, &normals};
-    return launch(L->f[K_SCAN], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_imu(uint64_t hash, const float *root, const float *dof, int n, const ImuArgs &ia, const float *bias,
-                   const int64_t *reset, float *history, float *out, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    ImuArgs aa = ia;
-    void *args[] = {&root, &dof, &n, &aa, &bias, &reset, &history, &out};
-    return launch(L->f[K_IMU], (unsigned)n, 64, 0, stream, args);
-}
-
-int jit_launch_ray_cast(uint64_t hash, const float *root, const float *dof, const float *rays, int n,
-                        const RayArgs &ra, float *dist, float *normals, hipStream_t stream) {
-    JitLoaded *L = find(hash);
-    if (!L) return TG_ERR_MODEL;
-    RayArgs aa = ra;
-    void *args[] = {&root, &dof, &rays, &n, &aa, &dist, &normals};
-    return launch(L->f[K_RAY], (unsigned)n * (unsigned)ray_chunks(ra), 64, 0, stream, args);
+    if (!L || kernel < 0 || kernel >= OD_COUNT) return TG_ERR_MODEL;
+    return launch(L->f[K_ON_DEMAND + kernel], grid, block, 0, stream, args);
 }
 
 }  // namespace tg

@@ -226,14 +226,36 @@ struct PaperPostArgs {
     int nblk;              // term-7 blocks (workgroups) of this launch
 };
 
-// launch figures that the kernels (articulation_kernels.h) and both host
-// launch paths (articulation.hip, jit.cpp) share
+// launch figures that the kernels (articulation_kernels.h) and the host
+// launchers (articulation.hip, jit.cpp's step) share
 // COMPOSE_WPB wavefronts per workgroup, one env each: a launch over all envs
 // is N / COMPOSE_WPB workgroups (most waves exit at once), not N
 constexpr int COMPOSE_WPB = 8;
 constexpr int JAC_THREADS = 256;   // threads per env of jacobian_kernel
 
 #ifndef __HIPCC_RTC__   // host launchers (not part of a hipRTC unit, jit.cpp)
+// the on-demand kernels (articulation_kernels.h): one launch per call for a model, not part of the step.  Each is
+// named here once, X(identifier, kernel template); from this list articulation.hip takes the compiled-in instantiations
+// of its dispatch (on_demand) and jit.cpp the name expressions and the functions of a run-time model, in this order (a
+// changed order is a changed cache file: jit.cpp's magic).  A new kernel is the template, an entry here, its launch_*
+// (declared below, one statement in articulation.hip) and the C-ABI entry (tgsim_api.cpp)
+#define TG_FOR_EACH_ON_DEMAND(X)                   \
+    X(BODY, body_state_kernel)                     \
+    X(RBF, rb_force_kernel)                        \
+    X(JAC, jacobian_kernel)                        \
+    X(MASS, mass_matrix_kernel)                    \
+    X(IK, ik_dls_kernel)                           \
+    X(OSC, osc_kernel)                             \
+    X(ID, inverse_dynamics_kernel)                 \
+    X(CENTROIDAL, centroidal_kernel)               \
+    X(CID, contact_inverse_dynamics_kernel)        \
+    X(SCAN, height_scan_kernel)                    \
+    X(IMU, imu_kernel)                             \
+    X(RAY, ray_cast_kernel)
+#define TG_OD_ENUM(ID, KERNEL) OD_##ID,
+enum OnDemandKernel { TG_FOR_EACH_ON_DEMAND(TG_OD_ENUM) OD_COUNT };
+#undef TG_OD_ENUM
+
 // what rides on a step: one fused task epilogue (post-physics in the step
 // kernel) at the most, or the force exports -- cf [N, L, 3], the net contact
 // force of every link that carries a shape (step_par.h NoPostCF), and df
@@ -320,35 +342,9 @@ int jit_compile(uint64_t hash, const char *struct_name, const char *model_source
 bool jit_has(uint64_t hash);
 int jit_kc(uint64_t hash);
 int jit_launch_step(uint64_t hash, const StepArgs &a, hipStream_t stream, hipEvent_t ev_begin, hipEvent_t ev_end);
-int jit_launch_body_states(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
-int jit_launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
-                         const float *mass_scale, const float *forces, const float *torques, int space, float *out,
-                         const float *props, hipStream_t stream);
-int jit_launch_jacobians(uint64_t hash, const float *root, const float *dof, int n, float *out, hipStream_t stream);
-int jit_launch_mass_matrices(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
-                             const float *props, int n, float *out, hipStream_t stream);
-int jit_launch_ik_dls(uint64_t hash, const float *root, const float *dof, int n, const IkChains &ch, int K,
-                      const float *goal_pos, const float *goal_quat, float lambda2, float *dq, float *err,
-                      float *pos_targets, hipStream_t stream);
-int jit_launch_osc(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props,
-                   int n, const IkChains &ch, int K, const float *goal_pos, const float *goal_quat,
-                   const float *q_rest, const OscGains &gains, float *tau, float *err, float *efforts,
-                   hipStream_t stream);
-int jit_launch_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
-                                const float *props, int n, const IdArgs &ia, const float *accel, float *tau,
-                                float *efforts, hipStream_t stream);
-int jit_launch_contact_inverse_dynamics(uint64_t hash, const float *root, const float *dof, const float *mass_scale,
-                                        const float *props, int n, const IdArgs &ia, const CidArgs &ca,
-                                        const float *share, const float *accel, float *tau, float *wrench,
-                                        float *efforts, hipStream_t stream);
-int jit_launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n,
-                          float *state, float *matrix, float *bias, hipStream_t stream);
-int jit_launch_height_scan(uint64_t hash, const float *root, const float *dof, const float *points, int n,
-                           const ScanArgs &sa, float *heights, float *normals, hipStream_t stream);
-int jit_launch_imu(uint64_t hash, const float *root, const float *dof, int n, const ImuArgs &ia, const float *bias,
-                   const int64_t *reset, float *history, float *out, hipStream_t stream);
-int jit_launch_ray_cast(uint64_t hash, const float *root, const float *dof, const float *rays, int n,
-                        const RayArgs &ra, float *dist, float *normals, hipStream_t stream);
+// on-demand kernel `kernel` (an OnDemandKernel) of a run-time model, without dynamic LDS; args: hipModuleLaunchKernel's
+// array of pointers to the arguments, which articulation.hip forms from the kernel's own parameter types (on_demand)
+int jit_launch(uint64_t hash, int kernel, unsigned grid, unsigned block, hipStream_t stream, void **args);
 
 int launch_gogoro_pre(const tg_gogoro_params &p, const tg_gogoro_buffers &b, const float *actions,
                       const float *pre_draws, uint64_t counter, hipStream_t stream);

@@ -171,6 +171,36 @@ int check_ids(tg_sim *s, const int32_t *ids, int32_t n) {
     if (n > 0 && !ids) return fail(TG_ERR_ARG, "null index pointer with n=%d", n);
     return 0;
 }
+// the sim's heightfield of this moment (null: no terrain) into any kernel argument struct that has the members
+// ground_at (ground.h) reads: StepArgs, ScanArgs, RayArgs
+template <class A> void heightfield_args(const tg_sim *s, A &a) {
+    a.hf = s->hf_rows > 0 ? s->hf : nullptr;
+    a.hf_rows = s->hf_rows;
+    a.hf_cols = s->hf_cols;
+    a.hf_hs = s->hf_hs;
+    a.hf_vs = s->hf_vs;
+    a.hf_ox = s->hf_ox;
+    a.hf_oy = s->hf_oy;
+}
+// The link frames of a sensor call (tg_height_scan, tg_imu, tg_ray_cast), in the two phases of their checks.  L < 0,
+// before the sim is looked at: no negative link and no offset that is not finite, and the frames are copied to dst.
+// Otherwise, after it: every link within the model's L.  what: the word of the messages, "frame" or "sensor"
+int check_link_frames(const char *fn, const char *what, const tg_contact_frame *f, int n, int L,
+                      tg_contact_frame *dst = nullptr) {
+    for (int k = 0; k < n; ++k) {
+        if (L >= 0) {
+            if (f[k].link >= L)
+                return fail(TG_ERR_ARG, "%s: %s %d: link %d outside [0, %d)", fn, what, k, f[k].link, L);
+            continue;
+        }
+        if (f[k].link < 0) return fail(TG_ERR_ARG, "%s: %s %d: link %d is negative", fn, what, k, f[k].link);
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(f[k].offset[i]))
+                return fail(TG_ERR_ARG, "%s: %s %d: offset[%d] is not finite", fn, what, k, i);
+        dst[k] = f[k];
+    }
+    return 0;
+}
 tg::StepArgs step_args(tg_sim *s) {
     tg::StepArgs a{};
     const tg_sim_params &p = s->params;
@@ -206,13 +236,7 @@ tg::StepArgs step_args(tg_sim *s) {
     a.dirty = s->dirty;
     a.err = s->err;
     a.cuni = s->uni_ok ? s->cuni : nullptr;
-    a.hf = s->hf_rows > 0 ? s->hf : nullptr;
-    a.hf_rows = s->hf_rows;
-    a.hf_cols = s->hf_cols;
-    a.hf_hs = s->hf_hs;
-    a.hf_vs = s->hf_vs;
-    a.hf_ox = s->hf_ox;
-    a.hf_oy = s->hf_oy;
+    heightfield_args(s, a);
     a.hf_mu = s->hf_mu;
     return a;
 }
@@ -934,13 +958,7 @@ int tg_height_scan(tg_sim *s, const tg_contact_frame *frames, int32_t num_frames
     if (num_points < 1 || num_points > TG_SCAN_MAX_POINTS)
         return fail(TG_ERR_ARG, "%s: num_points %d outside 1..%d", fn, num_points, TG_SCAN_MAX_POINTS);
     tg::ScanArgs sa{};
-    for (int k = 0; k < num_frames; ++k) {
-        if (frames[k].link < 0) return fail(TG_ERR_ARG, "%s: frame %d: link %d is negative", fn, k, frames[k].link);
-        for (int i = 0; i < 3; ++i)
-            if (!std::isfinite(frames[k].offset[i]))
-                return fail(TG_ERR_ARG, "%s: frame %d: offset[%d] is not finite", fn, k, i);
-        sa.f[k] = frames[k];
-    }
+    if (int rc = check_link_frames(fn, "frame", frames, num_frames, -1, sa.f)) return rc;
     const tg_scan_params &p = *params;
     if (p.surface != TG_SCAN_SURFACE && p.surface != TG_SCAN_CELL)
         return fail(TG_ERR_ARG, "%s: surface %d is neither TG_SCAN_SURFACE nor TG_SCAN_CELL", fn, p.surface);
@@ -957,20 +975,11 @@ int tg_height_scan(tg_sim *s, const tg_contact_frame *frames, int32_t num_frames
         return fail(TG_ERR_ARG, "%s: TG_SCAN_CELL has no normals: normals must be null", fn);
     if (!heights && !normals) return fail(TG_ERR_ARG, "%s: heights and normals are both null", fn);
     if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
-    for (int k = 0; k < num_frames; ++k)
-        if (frames[k].link >= s->L)
-            return fail(TG_ERR_ARG, "%s: frame %d: link %d outside [0, %d)", fn, k, frames[k].link, s->L);
+    if (int rc = check_link_frames(fn, "frame", frames, num_frames, s->L)) return rc;
     sa.F = num_frames;
     sa.P = num_points;
     sa.p = p;
-    // the heightfield of this moment (step_args hands the step kernel the same members)
-    sa.hf = s->hf_rows > 0 ? s->hf : nullptr;
-    sa.hf_rows = s->hf_rows;
-    sa.hf_cols = s->hf_cols;
-    sa.hf_hs = s->hf_hs;
-    sa.hf_vs = s->hf_vs;
-    sa.hf_ox = s->hf_ox;
-    sa.hf_oy = s->hf_oy;
+    heightfield_args(s, sa);
     DeviceGuard dg(s->device);
     win_touch(s);
     if (int rc = tg::launch_height_scan(s->hash, s->root, s->dof, points, (int)s->N, sa, heights, normals, s->stream))
@@ -988,13 +997,7 @@ int tg_imu(tg_sim *s, const tg_contact_frame *sensors, int32_t num_sensors, cons
     if (num_sensors < 1 || num_sensors > TG_IMU_MAX_SENSORS)
         return fail(TG_ERR_ARG, "%s: num_sensors %d outside 1..%d", fn, num_sensors, TG_IMU_MAX_SENSORS);
     tg::ImuArgs ia{};
-    for (int k = 0; k < num_sensors; ++k) {
-        if (sensors[k].link < 0) return fail(TG_ERR_ARG, "%s: sensor %d: link %d is negative", fn, k, sensors[k].link);
-        for (int i = 0; i < 3; ++i)
-            if (!std::isfinite(sensors[k].offset[i]))
-                return fail(TG_ERR_ARG, "%s: sensor %d: offset[%d] is not finite", fn, k, i);
-        ia.s[k] = sensors[k];
-    }
+    if (int rc = check_link_frames(fn, "sensor", sensors, num_sensors, -1, ia.s)) return rc;
     const tg_imu_params &p = *params;
     if (!std::isfinite(p.gyro_noise) || p.gyro_noise < 0.f)
         return fail(TG_ERR_ARG, "%s: gyro_noise %g is not a finite number >= 0", fn, (double)p.gyro_noise);
@@ -1003,9 +1006,7 @@ int tg_imu(tg_sim *s, const tg_contact_frame *sensors, int32_t num_sensors, cons
     if (history && !(std::isfinite(p.dt) && p.dt > 0.f))
         return fail(TG_ERR_ARG, "%s: history with a dt %g that is not a finite number > 0", fn, (double)p.dt);
     if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
-    for (int k = 0; k < num_sensors; ++k)
-        if (sensors[k].link >= s->L)
-            return fail(TG_ERR_ARG, "%s: sensor %d: link %d outside [0, %d)", fn, k, sensors[k].link, s->L);
+    if (int rc = check_link_frames(fn, "sensor", sensors, num_sensors, s->L)) return rc;
     ia.S = num_sensors;
     memcpy(ia.g, s->gravity, sizeof ia.g);   // the gravity of this moment
     ia.dt = p.dt;
@@ -1035,34 +1036,19 @@ int tg_ray_cast(tg_sim *s, const tg_contact_frame *frames, int32_t num_frames, c
     if (num_rays < 1 || num_rays > TG_RAY_MAX_RAYS)
         return fail(TG_ERR_ARG, "%s: num_rays %d outside 1..%d", fn, num_rays, TG_RAY_MAX_RAYS);
     tg::RayArgs ra{};
-    for (int k = 0; k < num_frames; ++k) {
-        if (frames[k].link < 0) return fail(TG_ERR_ARG, "%s: frame %d: link %d is negative", fn, k, frames[k].link);
-        for (int i = 0; i < 3; ++i)
-            if (!std::isfinite(frames[k].offset[i]))
-                return fail(TG_ERR_ARG, "%s: frame %d: offset[%d] is not finite", fn, k, i);
-        ra.f[k] = frames[k];
-    }
+    if (int rc = check_link_frames(fn, "frame", frames, num_frames, -1, ra.f)) return rc;
     const tg_ray_params &p = *params;
     if (p.align != TG_RAY_LINK && p.align != TG_RAY_YAW && p.align != TG_RAY_WORLD)
         return fail(TG_ERR_ARG, "%s: align %d is none of TG_RAY_LINK, TG_RAY_YAW, TG_RAY_WORLD", fn, p.align);
     if (!(std::isfinite(p.max_range) && p.max_range > 0.f))
         return fail(TG_ERR_ARG, "%s: max_range %g is not a finite number > 0", fn, (double)p.max_range);
     if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
-    for (int k = 0; k < num_frames; ++k)
-        if (frames[k].link >= s->L)
-            return fail(TG_ERR_ARG, "%s: frame %d: link %d outside [0, %d)", fn, k, frames[k].link, s->L);
+    if (int rc = check_link_frames(fn, "frame", frames, num_frames, s->L)) return rc;
     ra.F = num_frames;
     ra.R = num_rays;
     ra.align = p.align;
     ra.max_range = p.max_range;
-    // the heightfield of this moment (step_args hands the step kernel the same members)
-    ra.hf = s->hf_rows > 0 ? s->hf : nullptr;
-    ra.hf_rows = s->hf_rows;
-    ra.hf_cols = s->hf_cols;
-    ra.hf_hs = s->hf_hs;
-    ra.hf_vs = s->hf_vs;
-    ra.hf_ox = s->hf_ox;
-    ra.hf_oy = s->hf_oy;
+    heightfield_args(s, ra);
     ra.hf_zcap = s->hf_zcap;
     DeviceGuard dg(s->device);
     win_touch(s);
@@ -1362,6 +1348,16 @@ int tg_walk_pre_physics(tg_sim *s, const tg_walk_params *p, const tg_walk_buffer
     return TG_OK;
 }
 
+// pre_physics_step as the prologue of a simulate (StepArgs pm_*)
+static void walk_pre_args(tg::StepArgs &a, const tg_walk_params *p, const tg_walk_buffers *b, const float *actions) {
+    a.pm_actions = actions;
+    a.pm_act_out = b->actions;
+    a.pm_tgt_out = b->pos_target;
+    a.pm_scale = p->action_scale;
+    a.pm_clip = p->clip_actions;
+    for (int d = 0; d < p->num_dof; ++d) a.pm_default[d] = p->default_pos[d];
+}
+
 int tg_walk_step(tg_sim *s, const tg_walk_params *p, const tg_walk_buffers *b, const float *actions,
                  int32_t n_simulate, const float *reset_draws, const float *push_draws, uint64_t counter) {
     if (int rc = check_walk(s, p, b)) return rc;
@@ -1379,12 +1375,7 @@ int tg_walk_step(tg_sim *s, const tg_walk_params *p, const tg_walk_buffers *b, c
         // actions where pass 2a loads them), physics and post-physics all in
         // the step kernel; the compose launch runs only if an env may be dirty
         tg::StepArgs a = step_args(s);
-        a.pm_actions = actions;
-        a.pm_act_out = b->actions;
-        a.pm_tgt_out = b->pos_target;
-        a.pm_scale = p->action_scale;
-        a.pm_clip = p->clip_actions;
-        for (int d = 0; d < p->num_dof; ++d) a.pm_default[d] = p->default_pos[d];
+        walk_pre_args(a, p, b, actions);
         a.pm_in_step = 1;
         const tg::WalkPostArgs wp{*p, *b, reset_draws, push_draws, (uint32_t)counter, (uint32_t)(counter >> 32)};
         tg::StepPost post;
@@ -1395,14 +1386,7 @@ int tg_walk_step(tg_sim *s, const tg_walk_params *p, const tg_walk_buffers *b, c
     }
     for (int i = 0; i < n_simulate; ++i) {
         tg::StepArgs a = step_args(s);
-        if (i == 0) {   // pre_physics_step fused into the first compose launch
-            a.pm_actions = actions;
-            a.pm_act_out = b->actions;
-            a.pm_tgt_out = b->pos_target;
-            a.pm_scale = p->action_scale;
-            a.pm_clip = p->clip_actions;
-            for (int d = 0; d < p->num_dof; ++d) a.pm_default[d] = p->default_pos[d];
-        }
+        if (i == 0) walk_pre_args(a, p, b, actions);   // pre_physics_step fused into the first compose launch
         if (i == n_simulate - 1 && !s->walk_unfused) {   // post-physics fused into the last step kernel
             const tg::WalkPostArgs wp{*p, *b, reset_draws, push_draws, (uint32_t)counter, (uint32_t)(counter >> 32)};
             tg::StepPost post;
@@ -1542,20 +1526,9 @@ int tg_paper_step(tg_sim *s, const tg_paper_params *p, const tg_paper_buffers *b
         tg::StepArgs a = step_args(s);
         if (i == 0) {   // pre_physics_step as the first compose launch's prologue
             tg::PaperPre &q = a.pp;
-            q.actions = actions;
-            q.command_history = b->command_history;
-            q.steer_delay = b->steer_delay;
-            q.curent_speed = b->curent_speed;
-            q.curent_command = b->curent_command;
-            q.pos_target = b->pos_target;
-            q.vel_target = b->vel_target;
-            q.max_steering = p->max_steering;
-            q.use_steer_delay = p->use_steer_delay;
-            q.dof_steer = p->dof_steer;
-            q.dof_rear = p->dof_rear;
+            q = paper_pre_args(p, b, actions);
             // in the step kernel itself when it is the only simulate and the
             // model's kernel has the pre-physics slots; else the compose prologue
-            q.actions = actions;
             // (FUSED bit 4: the bit the step kernel tests before it runs the
             // paper pre-physics and forms the term-7 partials)
             a.pp_in_step = (n_simulate == 1 && (tg::model_info(s->hash).fused & 4) && !s->pre_in_compose) ? 1 : 0;
