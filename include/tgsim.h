@@ -96,6 +96,10 @@
  *   tg_ray_cast              (no counterpart) lidar and depth-camera ranges: rays
  *                            cast from link frames against the heightfield
  *                            solid and the z = 0 plane
+ *   tg_proximity             (no counterpart) self-collision sensing: signed
+ *                            distances between capsules on the robot's own
+ *                            links, their witness points and a per-env summary
+ *                            (smallest distance, count and penalty under a margin)
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -987,6 +991,62 @@ int tg_ray_cast(tg_sim *sim, const tg_contact_frame *frames /* HOST */, int32_t 
                 const tg_ray_params *params /* HOST */,
                 float *dist /* [N, F, R] device or NULL */,
                 float *normals /* [N, F, R, 3] device or NULL */);
+/* Self-collision sensing in one kernel: the signed distances between pairs of
+ * capsules fixed to the robot's own links, optionally their witness points and
+ * a per-env summary -- what a policy needs to be kept from crossing its legs
+ * or swinging a forearm through the chest.  The step models contact with the
+ * ground only; this call is a sensor, there is no contact response between
+ * links.  On demand, stream-ordered, from the current root and dof state;
+ * nothing of the sim is written and nothing is kept on the host between calls.
+ * A NULL output is not touched; every element of every non-NULL output is
+ * written.
+ *
+ * Capsule k on link l has the world axis
+ *   x(s) = o_l + R_l (p0 + s (p1 - p0)),   s in [0, 1]
+ * (o_l and R_l those of tg_rigid_body_states) and the radius r_k; p0 == p1 is
+ * a sphere.  Two capsules on the same link are allowed.  pairs [P, 2] holds
+ * indices into capsules; for pair p = (a, b), delta is the least distance
+ * between the two axis segments, and
+ *   dist[e, p]    = delta - r_a - r_b; a negative value is the penetration
+ *                   depth
+ *   witness[e, p] = a minimising point on axis a (3), then one on axis b (3),
+ *                   in world coordinates; where the minimiser is not unique
+ *                   (parallel, overlapping axes) any minimiser may be returned
+ *   summary[e]    = [0] the smallest dist over the pairs
+ *                   [1] the lowest pair index that attains it, as a float
+ *                   [2] the number of pairs with dist < margin
+ *                   [3] sum_p max(0, margin - dist_p), the self-collision
+ *                       penalty of a reward
+ * The link poses are formed relative to the root link's origin and the root
+ * position is added last, and only to witness: dist and summary do not depend
+ * on where the env stands.  summary is reduced in a fixed order, so it is
+ * bit-reproducible from call to call.  Envs do not interact.  The kernel forms
+ * no index from device data; the distances of a non-finite state are not
+ * specified, the call stays memory-safe.
+ *
+ * TG_ERR_ARG (message "tg_proximity: ...") with nothing launched, in this
+ * order: a null sim, null capsules, pairs or params, num_capsules outside
+ * 1..TG_PROX_MAX_CAPSULES, num_pairs outside 1..TG_PROX_MAX_PAIRS, a link
+ * outside [0, L), a non-finite end point or radius or a negative radius, a
+ * pair index outside [0, C) or a pair of a capsule with itself, a non-finite
+ * margin, all three outputs NULL.  Every model, run-time (tg_model_jit) ones
+ * included. */
+#define TG_PROX_MAX_CAPSULES 32
+#define TG_PROX_MAX_PAIRS    256
+typedef struct tg_capsule {      /* HOST, read during the call */
+    int32_t link;                /* [0, L) */
+    float p0[3], p1[3];          /* axis end points in the link frame; p0 == p1: a sphere */
+    float radius;                /* >= 0 */
+} tg_capsule;                    /* 32 bytes */
+typedef struct tg_proximity_params {   /* HOST, read during the call */
+    float margin;
+} tg_proximity_params;           /* 4 bytes */
+int tg_proximity(tg_sim *sim, const tg_capsule *capsules /* HOST */, int32_t num_capsules,
+                 const int32_t *pairs /* HOST [P, 2], indices into capsules */, int32_t num_pairs,
+                 const tg_proximity_params *params /* HOST */,
+                 float *dist /* [N, P] device or NULL */,
+                 float *witness /* [N, P, 6] device or NULL */,
+                 float *summary /* [N, 4] device or NULL */);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

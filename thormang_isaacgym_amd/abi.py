@@ -120,6 +120,21 @@ class tg_ray_params(C.Structure):
 
 assert C.sizeof(tg_ray_params) == 8
 
+TG_PROX_MAX_CAPSULES, TG_PROX_MAX_PAIRS = 32, 256   # capsules and pairs of one tg_proximity call
+
+
+class tg_capsule(C.Structure):
+    """One capsule of tg_proximity (tgsim.h): the link, the axis end points in its frame, the radius."""
+    _fields_ = [("link", C.c_int32), ("p0", C.c_float * 3), ("p1", C.c_float * 3), ("radius", C.c_float)]
+
+
+class tg_proximity_params(C.Structure):
+    """The margin under which tg_proximity's summary counts and penalises a pair (tgsim.h)."""
+    _fields_ = [("margin", C.c_float)]
+
+
+assert C.sizeof(tg_capsule) == 32 and C.sizeof(tg_proximity_params) == 4
+
 
 class tg_osc_gains(C.Structure):
     """The gains of tg_osc (tgsim.h): task-space kp / kd, null-space kp_null / kd_null, the damping lambda."""

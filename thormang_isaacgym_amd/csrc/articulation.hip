@@ -226,6 +226,11 @@ int launch_ray_cast(uint64_t hash, const float *root, const float *dof, const fl
                              normals);
 }
 
+int launch_proximity(uint64_t hash, const float *root, const float *dof, int n, const ProxArgs &pa, float *dist,
+                     float *witness, float *summary, hipStream_t stream) {
+    return on_demand<OD_PROX>(hash, n, 64, stream, root, dof, n, pa, dist, witness, summary);
+}
+
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {

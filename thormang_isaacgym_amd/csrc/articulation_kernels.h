@@ -2416,6 +2416,135 @@ __global__ __launch_bounds__(64) void ray_cast_kernel(const float *root, const f
     }
 }
 
+// The closest points of the segments p1 + s d1 and p2 + t d2, s, t in [0, 1] (Ericson, Real-Time Collision Detection
+// 5.1.9): the unclamped s of the two lines, clamped; the t that is best for that s; where that t leaves [0, 1] it is
+// clamped and s is formed again for it, so that a poorly conditioned first s (near-parallel axes: its denominator is
+// |d1 x d2|^2, taken from the cross product, which cannot come out negative) moves the points along the axes but
+// not apart.  A zero-length axis (squared length <= PROX_ZERO2, a micrometre) is a point.
+constexpr float PROX_ZERO2 = 1e-12f;
+__device__ __forceinline__ void segment_closest(V3 p1, V3 d1, V3 p2, V3 d2, float &s, float &t) {
+    auto unit = [](float x) { return fminf(fmaxf(x, 0.f), 1.f); };
+    const V3 r = p1 - p2;
+    const float a = dot(d1, d1), e = dot(d2, d2), f = dot(d2, r);
+    s = 0.f;
+    t = 0.f;
+    if (a <= PROX_ZERO2) {
+        if (e > PROX_ZERO2) t = unit(f / e);
+        return;
+    }
+    const float c = dot(d1, r);
+    if (e <= PROX_ZERO2) {
+        s = unit(-c / a);
+        return;
+    }
+    const float b = dot(d1, d2);
+    const V3 x = cross(d1, d2);
+    const float denom = dot(x, x);
+    if (denom > 0.f) s = unit((b * f - c * e) / denom);
+    const float tn = b * s + f;
+    if (tn < 0.f) {
+        s = unit(-c / a);
+    } else if (tn > e) {
+        t = 1.f;
+        s = unit((b - c) / a);
+    } else {
+        t = tn / e;
+    }
+}
+
+// Proximity (tgsim.h tg_proximity): the signed distances dist [N, P] between P pairs of C capsules on link frames,
+// their witness points [N, P, 6] and the summary [N, 4] (smallest distance, its first pair, the count and the
+// penalty under the margin).  One wavefront per env:
+//   lanes          forward kinematics (fk_root_relative)
+//   lane = capsule the two end points of its axis relative to the root origin and the radius -- eight floats per
+//                  capsule in LDS
+//   lanes          stride over the pairs in output order, so that a wave stores 256 contiguous bytes of dist per pass:
+//                  segment_closest on the relative end points, the root position added last and to the witness points
+//                  only; each lane keeps the smallest distance, its pair, the count and the penalty of its pairs in
+//                  increasing pair order
+//   xor butterfly  of the four over the wave: the smaller distance wins, the lower pair on a tie; a fixed order, so the
+//                  summary has the same bits from call to call
+// The capsules and the pairs are kernel arguments (ProxArgs): no index is formed from device data.  Which outputs are
+// null is uniform over the launch.  Wave-level syncs only, plain stores, no atomics.
+template <class M>
+__global__ __launch_bounds__(64) void proximity_kernel(const float *root, const float *dof, int n, ProxArgs a,
+                                                       float *dist, float *witness, float *summary) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    __shared__ float T[M::NL][12], A[M::NL][3];
+    __shared__ __align__(16) float CP[TG_PROX_MAX_CAPSULES][8];   // p0 (3), the radius, p1 (3), a pad
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e;
+    fk_root_relative<M>(r, dof + 2 * (size_t)e * M::ND, lane, T, A);
+    if (lane < a.C) {
+        const tg_capsule &c = a.c[lane];
+        const int l = min(max(c.link, 0), M::NL - 1);   // (the host has checked it: [0, L))
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const V3 o = v3(T[l][9], T[l][10], T[l][11]);
+        const V3 p0 = o + mul(R, v3(c.p0[0], c.p0[1], c.p0[2])), p1 = o + mul(R, v3(c.p1[0], c.p1[1], c.p1[2]));
+        *reinterpret_cast<float4 *>(CP[lane]) = make_float4(p0.x, p0.y, p0.z, c.radius);
+        *reinterpret_cast<float4 *>(CP[lane] + 4) = make_float4(p1.x, p1.y, p1.z, 0.f);
+    }
+    wsync();
+    const int P = a.P;
+    const size_t base = (size_t)e * P;
+    const V3 ro = v3(r[0], r[1], r[2]);
+    float best = 3.0e38f, pen = 0.f;
+    int first = P, count = 0;
+    for (int p = lane; p < P; p += 64) {
+        const int ia = min((int)a.pair[p][0], TG_PROX_MAX_CAPSULES - 1);
+        const int ib = min((int)a.pair[p][1], TG_PROX_MAX_CAPSULES - 1);
+        const float4 a0 = *reinterpret_cast<const float4 *>(CP[ia]);
+        const float4 a1 = *reinterpret_cast<const float4 *>(CP[ia] + 4);
+        const float4 b0 = *reinterpret_cast<const float4 *>(CP[ib]);
+        const float4 b1 = *reinterpret_cast<const float4 *>(CP[ib] + 4);
+        const V3 p1 = v3(a0.x, a0.y, a0.z), d1 = v3(a1.x, a1.y, a1.z) - p1;
+        const V3 p2 = v3(b0.x, b0.y, b0.z), d2 = v3(b1.x, b1.y, b1.z) - p2;
+        float s, t;
+        segment_closest(p1, d1, p2, d2, s, t);
+        const V3 wa = p1 + s * d1, wb = p2 + t * d2, sep = wa - wb;
+        const float d = sqrtf(dot(sep, sep)) - a0.w - b0.w;
+        if (dist) dist[base + p] = d;
+        if (witness) {
+            // the root position is added last: the distances do not depend on where the env sits
+            float *w = witness + (base + p) * 6;
+            const V3 ga = ro + wa, gb = ro + wb;
+            w[0] = ga.x; w[1] = ga.y; w[2] = ga.z;
+            w[3] = gb.x; w[4] = gb.y; w[5] = gb.z;
+        }
+        if (d < best) {   // (increasing p: the first pair of the lane that attains its smallest distance)
+            best = d;
+            first = p;
+        }
+        if (d < a.margin) ++count;
+        pen += fmaxf(a.margin - d, 0.f);
+    }
+    if (!summary) return;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ob = __shfl_xor(best, m, 64), op = __shfl_xor(pen, m, 64);
+        const int of = __shfl_xor(first, m, 64), oc = __shfl_xor(count, m, 64);
+        if (ob < best || (ob == best && of < first)) {
+            best = ob;
+            first = of;
+        }
+        count += oc;
+        pen += op;   // (a + b on both lanes of a pair: every lane holds the same bits)
+    }
+    if (lane == 0) {
+        float *o = summary + 4 * (size_t)e;
+        o[0] = best; o[1] = (float)first; o[2] = (float)count; o[3] = pen;
+    }
+}
+
 // ---------------------------------------------------------------- rigid-body forces
 // apply_rigid_body_force_tensors (reference call site
 // tasks/gogoro_realistic_turning_sim_paper.py:457): per-link forces [N*L,3] at

@@ -83,6 +83,18 @@ struct RayArgs {
 constexpr int RAY_CHUNK = TG_RAY_CHUNK;
 __host__ __device__ inline int ray_chunks(const RayArgs &a) { return (a.F * a.R + RAY_CHUNK - 1) / RAY_CHUNK; }
 
+// what a tg_proximity call hands proximity_kernel by value: the capsules as given, the pairs as byte pairs (capsule
+// indices are below TG_PROX_MAX_CAPSULES), the counts and the margin -- 1548 bytes, under the 4 KB of kernel arguments
+// on the compiled-in and on the hipModuleLaunchKernel path
+struct ProxArgs {
+    tg_capsule c[TG_PROX_MAX_CAPSULES];
+    uint8_t pair[TG_PROX_MAX_PAIRS][2];
+    int C, P;
+    float margin;
+};
+static_assert(sizeof(tg_capsule) == 32 && sizeof(ProxArgs) == 1548 && TG_PROX_MAX_CAPSULES <= 64,
+              "ProxArgs: lane = capsule, and a capsule index fits a byte");
+
 // the sensors of tg_set_force_sensor_tensor as the step kernel takes them by value (step_par.h NoPostFS): the
 // frames as registered, their count and the axes of the output (TG_ENV_SPACE / TG_LOCAL_SPACE)
 struct FsFrames {
@@ -251,7 +263,8 @@ constexpr int JAC_THREADS = 256;   // threads per env of jacobian_kernel
     X(CID, contact_inverse_dynamics_kernel)        \
     X(SCAN, height_scan_kernel)                    \
     X(IMU, imu_kernel)                             \
-    X(RAY, ray_cast_kernel)
+    X(RAY, ray_cast_kernel)                        \
+    X(PROX, proximity_kernel)
 #define TG_OD_ENUM(ID, KERNEL) OD_##ID,
 enum OnDemandKernel { TG_FOR_EACH_ON_DEMAND(TG_OD_ENUM) OD_COUNT };
 #undef TG_OD_ENUM
@@ -320,6 +333,10 @@ int launch_imu(uint64_t hash, const float *root, const float *dof, int n, const 
 // frames (ray_cast_kernel; tgsim.h tg_ray_cast)
 int launch_ray_cast(uint64_t hash, const float *root, const float *dof, const float *rays, int n, const RayArgs &ra,
                     float *dist, float *normals, hipStream_t stream);
+// capsule distances [N, P], witness points [N, P, 6] and the per-env summary [N, 4], each optional, of P pairs of the
+// C capsules on link frames (proximity_kernel; tgsim.h tg_proximity)
+int launch_proximity(uint64_t hash, const float *root, const float *dof, int n, const ProxArgs &pa, float *dist,
+                     float *witness, float *summary, hipStream_t stream);
 // per-link forces / torques [N*L,3] -> group wrenches [N,G,6] (rb_force_kernel)
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,

@@ -1057,6 +1057,53 @@ int tg_ray_cast(tg_sim *s, const tg_contact_frame *frames, int32_t num_frames, c
     return TG_OK;
 }
 
+int tg_proximity(tg_sim *s, const tg_capsule *capsules, int32_t num_capsules, const int32_t *pairs, int32_t num_pairs,
+                 const tg_proximity_params *params, float *dist, float *witness, float *summary) {
+    const char *fn = "tg_proximity";
+    // in the header's order: the sim, the pointers, the counts, the capsules, the pairs, the margin, the outputs
+    if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
+    if (!capsules) return fail(TG_ERR_ARG, "%s: null capsules", fn);
+    if (!pairs) return fail(TG_ERR_ARG, "%s: null pairs", fn);
+    if (!params) return fail(TG_ERR_ARG, "%s: null params", fn);
+    if (num_capsules < 1 || num_capsules > TG_PROX_MAX_CAPSULES)
+        return fail(TG_ERR_ARG, "%s: num_capsules %d outside 1..%d", fn, num_capsules, TG_PROX_MAX_CAPSULES);
+    if (num_pairs < 1 || num_pairs > TG_PROX_MAX_PAIRS)
+        return fail(TG_ERR_ARG, "%s: num_pairs %d outside 1..%d", fn, num_pairs, TG_PROX_MAX_PAIRS);
+    tg::ProxArgs pa{};
+    for (int k = 0; k < num_capsules; ++k)
+        if (capsules[k].link < 0 || capsules[k].link >= s->L)
+            return fail(TG_ERR_ARG, "%s: capsule %d: link %d outside [0, %d)", fn, k, capsules[k].link, (int)s->L);
+    for (int k = 0; k < num_capsules; ++k) {
+        const tg_capsule &c = capsules[k];
+        for (int i = 0; i < 3; ++i) {
+            if (!std::isfinite(c.p0[i])) return fail(TG_ERR_ARG, "%s: capsule %d: p0[%d] is not finite", fn, k, i);
+            if (!std::isfinite(c.p1[i])) return fail(TG_ERR_ARG, "%s: capsule %d: p1[%d] is not finite", fn, k, i);
+        }
+        if (!std::isfinite(c.radius) || c.radius < 0.f)
+            return fail(TG_ERR_ARG, "%s: capsule %d: radius %g is not a finite number >= 0", fn, k, (double)c.radius);
+        pa.c[k] = c;
+    }
+    for (int p = 0; p < num_pairs; ++p) {
+        const int32_t ia = pairs[2 * p], ib = pairs[2 * p + 1];
+        if (ia < 0 || ia >= num_capsules || ib < 0 || ib >= num_capsules)
+            return fail(TG_ERR_ARG, "%s: pair %d: (%d, %d) outside [0, %d)", fn, p, ia, ib, num_capsules);
+        if (ia == ib) return fail(TG_ERR_ARG, "%s: pair %d: capsule %d with itself", fn, p, ia);
+        pa.pair[p][0] = (uint8_t)ia;
+        pa.pair[p][1] = (uint8_t)ib;
+    }
+    if (!std::isfinite(params->margin))
+        return fail(TG_ERR_ARG, "%s: margin %g is not finite", fn, (double)params->margin);
+    if (!dist && !witness && !summary) return fail(TG_ERR_ARG, "%s: dist, witness and summary are all null", fn);
+    pa.C = num_capsules;
+    pa.P = num_pairs;
+    pa.margin = params->margin;
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_proximity(s->hash, s->root, s->dof, (int)s->N, pa, dist, witness, summary, s->stream))
+        return fail(rc, "%s: launch failed", fn);
+    return TG_OK;
+}
+
 int tg_set_net_contact_force_tensor(tg_sim *s, float *out) {
     if (int rc = check_sim(s)) return rc;
     if (!out) {

@@ -142,6 +142,64 @@ Centroidal = namedtuple("Centroidal", ["state", "matrix", "bias"])   # what Sim.
 ContactDynamics = namedtuple("ContactDynamics", ["tau", "wrench"])   # what Sim.contact_inverse_dynamics returns
 HeightScan = namedtuple("HeightScan", ["heights", "normals"])   # what Sim.height_scan returns
 RayCast = namedtuple("RayCast", ["dist", "normals"])   # what Sim.ray_cast returns
+Proximity = namedtuple("Proximity", ["dist", "witness", "summary"])   # what Sim.proximity returns
+
+
+def link_tree(model):
+    """(parent [L], joint origin position in the parent frame [L, 3]) of a model, read from its tg_model_desc: what
+    ``limb_capsule`` and ``capsule_pairs`` take.  ``model``: a ``Model``, or what owns a descriptor already (a
+    ``NativeModel``, an ``abi.ModelDesc``, a ``Sim``'s ``desc``)."""
+    owner = model if hasattr(model, "desc") else abi.ModelDesc(model)   # (kept alive while its arrays are read)
+    d = owner.desc
+    L = int(d.num_links)
+    parent = [int(d.link_parent[l]) for l in range(L)]
+    origin = np.array([[float(d.link_origin[12 * l + 9 + k]) for k in range(3)] for l in range(L)],
+                      np.float64).reshape(L, 3)
+    return parent, origin
+
+
+def make_capsule(link: int, p0, p1=None, radius: float = 0.05) -> abi.tg_capsule:
+    """The tg_capsule on link index ``link`` (``p1=None``: a sphere about ``p0``)."""
+    p0 = [float(v) for v in p0]
+    p1 = p0 if p1 is None else [float(v) for v in p1]
+    radius = float(radius)
+    if len(p0) != 3 or len(p1) != 3 or not all(math.isfinite(v) for v in p0 + p1):
+        raise ValueError("a capsule's end points are three finite numbers each")
+    if not (math.isfinite(radius) and radius >= 0.0):
+        raise ValueError(f"a capsule's radius is a finite number >= 0, got {radius}")
+    c = abi.tg_capsule()
+    c.link = int(link)
+    c.p0[:], c.p1[:], c.radius = p0, p1, radius
+    return c
+
+
+def limb_capsule(parent, origin, link: int, child: int, radius: float) -> abi.tg_capsule:
+    """The capsule from link ``link``'s origin to the origin of the joint that carries ``child`` (``link_tree``)."""
+    if parent[child] != link:
+        raise ValueError(f"link {child} is carried by link {parent[child]}, not by link {link}")
+    return make_capsule(link, (0.0, 0.0, 0.0), origin[child], radius)
+
+
+def link_hops(parent, a: int, b: int) -> int:
+    """The number of joints on the path between links ``a`` and ``b`` of the tree."""
+    up = {}
+    k, n = a, 0
+    while k >= 0:
+        up[k] = n
+        k, n = parent[k], n + 1
+    k, n = b, 0
+    while k not in up:
+        k, n = parent[k], n + 1
+    return up[k] + n
+
+
+def capsule_pairs(parent, capsules, min_hops: int = 3) -> list:
+    """The pairs (a, b), a < b, of ``capsules`` whose links are at least ``min_hops`` joints apart (``link_tree``)."""
+    pairs = [(a, b) for a in range(len(capsules)) for b in range(a + 1, len(capsules))
+             if link_hops(parent, int(capsules[a].link), int(capsules[b].link)) >= int(min_hops)]
+    if len(pairs) > abi.TG_PROX_MAX_PAIRS:
+        raise ValueError(f"{len(pairs)} pairs: a proximity call takes at most {abi.TG_PROX_MAX_PAIRS}")
+    return pairs
 # what Sim.imu returns: views of raw [N, S, 20]
 Imu = namedtuple("Imu", ["quat", "gravity", "lin_vel", "ang_vel", "lin_acc", "ang_acc", "valid", "raw"])
 
@@ -1038,6 +1096,104 @@ class Sim:
         check(lib().tg_ray_cast(self._h, arr, F, _ptr(rays), R, C.byref(rp), _ptr(dt), _ptr(nt)), "ray_cast")
         self._keep_rays = rays   # read on the sim stream; held until the next call
         return RayCast(dt, nt)
+
+    def capsule(self, link, p0, p1=None, radius: float = 0.05) -> abi.tg_capsule:
+        """One capsule of ``proximity`` (tgsim.h tg_capsule): the ``link`` it is
+        fixed to, by name or index, the end points ``p0`` and ``p1`` of its axis
+        in the link frame (``p1=None``: a sphere about ``p0``) and its
+        ``radius``."""
+        l = self._name_index("link", link)
+        if not 0 <= l < self.L:
+            raise ValueError(f"link {link!r} outside [0, {self.L})")
+        return make_capsule(l, p0, p1, radius)
+
+    def limb_capsule(self, link, child, radius: float) -> abi.tg_capsule:
+        """The capsule of the limb segment ``link``: from the link's origin to the
+        origin of the joint that carries ``child``, in the link frame -- the
+        thigh is ``limb_capsule("l_leg_hip_p_link", "l_leg_kn_p_link", r)``.
+        Raises if ``child``'s parent is not ``link``."""
+        parent, origin = link_tree(self.desc)
+        l, c = self._name_index("link", link), self._name_index("link", child)
+        if not (0 <= l < self.L and 0 <= c < self.L):
+            raise ValueError(f"links {link!r}, {child!r} outside [0, {self.L})")
+        return limb_capsule(parent, origin, l, c, radius)
+
+    def capsule_pairs(self, capsules, min_hops: int = 3) -> list:
+        """Every pair ``(a, b)``, ``a < b``, of ``capsules`` whose links are at
+        least ``min_hops`` joints apart in the link tree, in increasing order:
+        with the default, capsules on the same link, on a parent and its child
+        and on a grandparent and its grandchild (or two siblings) are left
+        out -- neighbours along a limb overlap by construction.  Raises above
+        256 pairs (tgsim.h TG_PROX_MAX_PAIRS)."""
+        return capsule_pairs(link_tree(self.desc)[0], capsules, min_hops)
+
+    def proximity(self, capsules, pairs, margin: float = 0.0, dist: bool = True, witness: bool = False,
+                  summary: bool = False, out: torch.Tensor | None = None, out_witness: torch.Tensor | None = None,
+                  out_summary: torch.Tensor | None = None) -> "Proximity":
+        """Capsule distances between the robot's own links in one kernel launch
+        (tgsim.h tg_proximity), from the current state, on the sim's stream.
+        ``capsules``: 1..32 ``capsule`` / ``limb_capsule``; ``pairs``: 1..256
+        pairs of indices into them (``capsule_pairs``).  Returns the named tuple
+        ``Proximity(dist, witness, summary)``, each None unless asked for:
+        ``dist`` [N, P], the distance between the two axis segments less the
+        two radii, negative by the penetration depth; ``witness`` [N, P, 6], a
+        closest point on the first axis and one on the second, world
+        coordinates; ``summary`` [N, 4], the smallest ``dist``, the lowest pair
+        index that attains it, the number of pairs with ``dist < margin`` and
+        ``sum_p max(0, margin - dist_p)``, a reward's self-collision penalty.
+        ``dist`` and ``summary`` do not depend on where the env stands, and
+        ``summary`` has the same bits from call to call.  ``out``,
+        ``out_witness`` and ``out_summary`` are checked and, for a requested
+        part, written and returned as given; without them the tensors are owned
+        by the sim, overwritten by the next call with as many pairs and
+        replaced by a call with another count."""
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        def own(key, shape):
+            buf = getattr(self, "_prox_out", None)
+            if buf is None:
+                buf = self._prox_out = {}
+            if key not in buf or tuple(buf[key].shape) != shape:   # one tensor per output: a new P replaces it
+                buf[key] = torch.zeros(*shape, dtype=torch.float32, device=self.device)
+            return buf[key]
+
+        margin = float(margin)
+        if not math.isfinite(margin):
+            raise ValueError(f"margin must be finite, got {margin}")
+        capsules = list(capsules)
+        Cn = len(capsules)
+        if not 1 <= Cn <= abi.TG_PROX_MAX_CAPSULES:
+            raise ValueError(f"proximity takes 1..{abi.TG_PROX_MAX_CAPSULES} capsules, got {Cn}")
+        if not all(isinstance(c, abi.tg_capsule) for c in capsules):
+            raise ValueError("capsules must be tg_capsule (Sim.capsule, Sim.limb_capsule)")
+        flat = np.ascontiguousarray(np.asarray(pairs, np.int64).reshape(-1, 2))
+        P = int(flat.shape[0])
+        if not 1 <= P <= abi.TG_PROX_MAX_PAIRS:
+            raise ValueError(f"proximity takes 1..{abi.TG_PROX_MAX_PAIRS} pairs, got {P}")
+        if flat.min() < 0 or flat.max() >= Cn or bool((flat[:, 0] == flat[:, 1]).any()):
+            raise ValueError(f"a pair must name two different capsules in [0, {Cn})")
+        if not (dist or witness or summary):
+            raise ValueError("proximity needs one of dist, witness and summary")
+        N = self.num_envs
+        shapes = {"out": (N, P), "out_witness": (N, P, 6), "out_summary": (N, 4)}
+        given = {"out": out, "out_witness": out_witness, "out_summary": out_summary}
+        for key, t in given.items():
+            if t is not None:
+                checked(t, shapes[key], key)
+        dt, wt, st = ((given[key] if given[key] is not None else own(key, shapes[key])) if asked else None
+                      for key, asked in (("out", dist), ("out_witness", witness), ("out_summary", summary)))
+        pp = abi.tg_proximity_params()
+        pp.margin = margin
+        arr = (abi.tg_capsule * Cn)(*capsules)
+        idx = (C.c_int32 * (2 * P))(*[int(v) for v in flat.reshape(-1)])
+        check(lib().tg_proximity(self._h, arr, Cn, idx, P, C.byref(pp), _ptr(dt), _ptr(wt), _ptr(st)), "proximity")
+        return Proximity(dt, wt, st)
 
     @property
     def contact_link_indices(self) -> list:

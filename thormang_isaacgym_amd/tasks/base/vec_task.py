@@ -324,6 +324,14 @@ class VecTask(Env):
         return self.sim.ray_cast(frames, rays, align=align, max_range=max_range, normals=normals, out=out,
                                  out_normals=out_normals)
 
+    def proximity(self, capsules, pairs, margin=0.0, dist=True, witness=False, summary=False, out=None,
+                  out_witness=None, out_summary=None):
+        """Signed distances [N, P] between the ``pairs`` of ``capsules`` on the robot's own links, optionally their
+        witness points [N, P, 6] and the summary [N, 4] -- smallest distance, its pair, count and penalty under
+        ``margin`` -- in one kernel (Sim.proximity)."""
+        return self.sim.proximity(capsules, pairs, margin=margin, dist=dist, witness=witness, summary=summary,
+                                  out=out, out_witness=out_witness, out_summary=out_summary)
+
     def imu(self, sensors, history=None, dt=None, reset=None, bias=None, gyro_noise=0.0, accel_noise=0.0, seed=0,
             counter=0, out=None):
         """IMU readings [N, S, 20] at the link frames ``sensors`` -- quaternion, projected gravity, body-frame

@@ -60,6 +60,18 @@ step reads ``valid = 0`` and zero accelerations instead of the jump.  An env
 reset through ``reset_idx`` from outside has its history dropped, to the same
 effect.  Observation, reward and reset do not read the extra, and the step
 itself is unchanged.
+
+``env.enableSelfProximity: true`` (optional, default false) adds
+``extras["self_proximity"]`` [N,4] after every step -- the summary of tgsim.h
+tg_proximity over the default capsule set (``walk_self_capsules``: pelvis,
+chest, head and per side upper arm, forearm, hand, thigh, shin and foot) and
+the pairs ``Sim.capsule_pairs`` makes of it, of the state the step returns
+with: the smallest distance between two limbs, its pair, and the count and
+the penalty ``sum max(0, margin - dist)`` under ``env.selfProximityMargin``
+(default 0.02 m), one extra kernel launch per step, for a self-collision
+penalty or termination a user adds.  At the default stance every pair is clear
+of the margin.  Observation, reward and reset do not read the extra, and the
+step itself is unchanged.
 """
 from __future__ import annotations
 
@@ -123,6 +135,7 @@ class ThormangWalk(VecTask):
         # simulate (legged tasks' foot-contact terms, tasks/anymal.py:113-117);
         # observation, reward and reset do not use them
         self.contact_forces = self.dof_forces = None
+        self.self_proximity = None   # (set before the first _contact_extras below; env.enableSelfProximity)
         if bool(env.get("enableContactForces", False)):
             self.contact_forces = self.acquire_net_contact_force_tensor()
             self.feet_indices = torch.as_tensor(walk_feet_indices(self.model), dtype=torch.long, device=dev)
@@ -153,6 +166,16 @@ class ThormangWalk(VecTask):
             self.imu_history = self.sim.imu_history(1)
             self.imu_raw = torch.zeros(N, 1, abi.TG_IMU_WIDTH, device=dev)
             self._imu_reset = torch.zeros(N, dtype=torch.int64, device=dev)
+        # env.enableSelfProximity: the smallest distance between the robot's own limbs, its pair, and the count and
+        # penalty under env.selfProximityMargin of the state a step returns with (tg_proximity); observation, reward
+        # and reset do not use them
+        if bool(env.get("enableSelfProximity", False)):
+            self.self_capsules = walk_self_capsules(self.model)
+            self.self_pairs = self.sim.capsule_pairs(self.self_capsules)
+            self.self_margin = float(env.get("selfProximityMargin", WALK_SELF_MARGIN))
+            self.self_proximity = torch.zeros(N, 4, device=dev)
+            # the set never changes: the argument arrays of tg_proximity are built and checked here, once
+            self._prox_args = proximity_args(self.self_capsules, self.self_pairs, self.self_margin)
         self.reset_idx(torch.arange(N, device=dev))
 
     # ------------------------------------------------------------ creation
@@ -246,6 +269,12 @@ class ThormangWalk(VecTask):
             self.sim.imu(self._imu_sensors, history=self.imu_history, dt=self.dt, reset=self._imu_reset,
                          out=self.imu_raw)
             self.extras["imu"] = self.imu_raw.to(self.rl_device)
+        # extras["self_proximity"] [N, 4]: the summary of the self-collision capsules (env.enableSelfProximity)
+        if self.self_proximity is not None:
+            arr, n_caps, idx, n_pairs, pp = self._prox_args
+            check(lib().tg_proximity(self.sim.handle, arr, n_caps, idx, n_pairs, C.byref(pp), None, None,
+                                     _p(self.self_proximity)), "tg_proximity")
+            self.extras["self_proximity"] = self.self_proximity.to(self.rl_device)
 
     def _imu_mark_resets(self):
         """The envs the coming step resets, for its IMU reading (env.enableImu): ``reset_buf`` as it stands before
@@ -302,6 +331,60 @@ def walk_feet_indices(m) -> list:
     carry a collision shape, as indices into ``m.links``."""
     from ..sim import contact_link_indices
     return [i for i in contact_link_indices(m) if "foot" in m.links[i].name]
+
+
+#: (name, link, child or end points, radius) of the walk's default self-collision set (walk_self_capsules): a child
+#: link makes the limb capsule from the link's origin to that child's joint; the per-side rows are mirrored for the
+#: right side (l_ -> r_, y -> -y).  The radii (0.03 .. 0.09 m) are set so that every default pair keeps the default
+#: margin of 0.02 m at the default stance with 5 mm to spare (asserted in tests/test_proximity_reference.py): the
+#: closest there are shin and foot, forearm and hand, pelvis and thigh, three joints apart each.  A capsule is a
+#: tube inside its link, for the sign of a distance and its trend, not the link's outline
+WALK_SELF_CAPSULES = (
+    ("pelvis", "pelvis_link", ((0.0, -0.04, 0.02), (0.0, 0.04, 0.02)), 0.055),
+    ("chest", "chest_link", ((0.0, 0.0, 0.04), (0.0, 0.0, 0.2)), 0.09),
+    ("head", "head_p_link", ((0.0, 0.045, 0.06), None), 0.08),
+)
+WALK_SELF_CAPSULES_SIDE = (
+    ("upper_arm", "l_arm_sh_p2_link", "l_arm_el_y_link", 0.05),
+    ("forearm", "l_arm_el_y_link", "l_arm_wr_r_link", 0.04),
+    ("hand", "l_arm_wr_p_link", "l_arm_end_link", 0.03),
+    ("thigh", "l_leg_hip_p_link", "l_leg_kn_p_link", 0.06),
+    ("shin", "l_leg_kn_p_link", "l_leg_an_p_link", 0.05),
+    ("foot", "l_leg_foot_link", ((-0.07, 0.014, -0.02), (0.07, 0.014, -0.02)), 0.03),
+)
+WALK_SELF_MARGIN = 0.02
+
+
+def walk_self_capsules(m) -> list:
+    """The walk's default self-collision capsules on model ``m`` (thormang, thormang_wb), as ``tg_capsule``: pelvis,
+    chest and head, then per side upper arm, forearm, hand, thigh, shin and a foot capsule along the sole."""
+    from ..sim import limb_capsule, link_tree, make_capsule
+    parent, origin = link_tree(m)
+    rows = list(WALK_SELF_CAPSULES)
+    for side, sy in (("l_", 1.0), ("r_", -1.0)):
+        for name, link, geom, radius in WALK_SELF_CAPSULES_SIDE:
+            if not isinstance(geom, str):
+                geom = tuple(None if p is None else (p[0], sy * p[1], p[2]) for p in geom)
+            else:
+                geom = side + geom[2:]
+            rows.append((side + name, side + link[2:], geom, radius))
+    out = []
+    for _name, link, geom, radius in rows:
+        l = m.link_index(link)
+        out.append(limb_capsule(parent, origin, l, m.link_index(geom), radius) if isinstance(geom, str)
+                   else make_capsule(l, geom[0], geom[1], radius))
+    return out
+
+
+def proximity_args(capsules, pairs, margin: float):
+    """(capsule array, C, flat pair array, P, params) of a tg_proximity call, for a set that is used every step."""
+    if not 1 <= len(capsules) <= abi.TG_PROX_MAX_CAPSULES or not 1 <= len(pairs) <= abi.TG_PROX_MAX_PAIRS:
+        raise ValueError(f"{len(capsules)} capsules, {len(pairs)} pairs: tg_proximity takes 1..32 and 1..256")
+    arr = (abi.tg_capsule * len(capsules))(*capsules)
+    idx = (C.c_int32 * (2 * len(pairs)))(*[int(v) for ab in pairs for v in ab])
+    pp = abi.tg_proximity_params()
+    pp.margin = float(margin)
+    return arr, len(capsules), idx, len(pairs), pp
 
 
 def walk_sole_centre(m, link: int):
