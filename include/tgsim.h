@@ -100,6 +100,12 @@
  *                            distances between capsules on the robot's own
  *                            links, their witness points and a per-env summary
  *                            (smallest distance, count and penalty under a margin)
+ *   tg_contact_qp            (no counterpart) whole-body inverse dynamics with the
+ *                            contact forces confined to friction cones and sole
+ *                            outlines: vertex forces of up to four rectangular
+ *                            patches by a fixed number of ADMM iterations, the
+ *                            joint torques that are left and the base wrench the
+ *                            ground cannot supply
  *   tg_get_sim_params / tg_set_sim_params
  *                            gym.get_sim_params / set_sim_params (vec_task.py:650-660)
  *   tg_sync                  fetch_results(sim, True) (vec_task.py:339)
@@ -1047,6 +1053,92 @@ int tg_proximity(tg_sim *sim, const tg_capsule *capsules /* HOST */, int32_t num
                  float *dist /* [N, P] device or NULL */,
                  float *witness /* [N, P, 6] device or NULL */,
                  float *summary /* [N, 4] device or NULL */);
+/* Contact forces inside friction cones and sole outlines in one kernel launch:
+ * tg_contact_inverse_dynamics with the distribution replaced by one that
+ * respects the contact model -- unilateral forces, Coulomb friction, the centre
+ * of pressure inside the sole -- so that the joint torques assume only wrenches
+ * the ground can supply, and what it cannot supply is reported.  On demand,
+ * stream-ordered, computed from the current root and dof state, the sim's
+ * current gravity, the env's body mass scales and its TG_PROP_ARMATURE and
+ * TG_PROP_EFFORT rows; nothing of the sim is written.  contacts, extents and
+ * dofs are HOST memory, read during the call and not retained (they travel to
+ * the kernel by value in its arguments).
+ *
+ * b = H a + h, p_k = o_l + R_l offset_k, c_root, Jp_k, terms, accel, efforts,
+ * dofs, num_dofs and accumulate are those of tg_contact_inverse_dynamics.
+ * Contact k of K (1..TG_CID_MAX_CONTACTS) is a rectangular patch on link l_k
+ * with the four vertices
+ *   p_kv = o_l + R_l (offset_k + (+-hx_k, +-hy_k, 0)),  v = 0..3 in the order (+,+), (+,-), (-,-), (-,+),
+ * (hx_k, hy_k) = extents[k] >= 0 the half extents in the link's x and y axes;
+ * zero extents give a point contact.  The unknowns are the J = 4 K vertex
+ * forces f_kv, world axes, acting on the robot, each confined to the friction
+ * cone of its contact:
+ *   C_k = { f : f.n_k >= 0, |f - (f.n_k) n_k| <= mu_k f.n_k }
+ * n_k from normals [N, K, 3] (e.g. tg_height_scan's), normalised in the kernel;
+ * a non-finite entry or a vector shorter than 1e-6 gives world z, NULL gives
+ * world z.  mu_k from friction [N, K], or the scalar mu where friction is NULL;
+ * negative and NaN values are taken as 0, values above 1e6 as 1e6.  With
+ * r_kv = p_kv - c_root, G_kv = [1; [r_kv]x] (6 x 3) and W = diag(1, 1, 1,
+ * 1/l^2, 1/l^2, 1/l^2), l = moment_arm > 0, the call approaches
+ *   minimise  1/2 |b[0:6] - sum G_kv f_kv|^2_W  +  1/2 reg sum_k (1/s_k) sum_v |f_kv|^2   over f_kv in C_k
+ * (moments about c_root, as the base rows of b are).  s_k >= 0 is the share
+ * (share [N, K]; NULL: all ones; negative and NaN values are taken as 0).  A
+ * contact with s_k = 0 is removed: its forces and its wrench are exactly 0.0
+ * and the env's other outputs equal those of a call without it.  An env with
+ * every s_k = 0 gets tau = b and makes no iterations.  The balance is soft on
+ * purpose: when b[0:6] is infeasible the answer is the nearest feasible one and
+ * the shortfall is returned in tau[0:6], not hidden.
+ *
+ * The algorithm is fixed, so that a reference can run the same one: over-relaxed
+ * ADMM in scaled form from z = u = 0.  With f the stacked vertex forces, G = [G_kv]
+ * (6 x 3 J), P = diag(reg / s_k + rho) and c = G^T W b[0:6], each of iters
+ * iterations is
+ *   q  = c + rho (z - u)
+ *   x  = P^-1 q - P^-1 G^T (W^-1 + G P^-1 G^T)^-1 G P^-1 q     (= (G^T W G + P)^-1 q; one 6 x 6 Cholesky factor per env)
+ *   xh = relax x + (1 - relax) z
+ *   z  = proj_C(xh + u)      per vertex, with w = xh + u, w_n = w.n, t = w - w_n n:
+ *                            w_n >= 0 and |t| <= mu w_n: w;  mu |t| <= -w_n: 0;
+ *                            else a (n + mu t / |t|), a = (mu |t| + w_n) / (1 + mu^2)
+ *   u  = u + xh - z
+ * and the result is z: every returned force lies in its cone by construction,
+ * after any number of iterations.  reg = 0.03, rho = 0.6, relax = 1.6 and
+ * iters = 64 are the values the Python binding passes (DESIGN.md 4.2 has
+ * their provenance).
+ *
+ * forces[e, k, v] = f_kv.  wrench[e, k] = (sum_v f_kv, sum_v (p_kv - p_k) x
+ * f_kv): force and moment about p_k, the convention of
+ * tg_contact_inverse_dynamics and of the force sensor tensor.  tau[6 + d] =
+ * b[6 + d] - sum_k Jp_k[:, 6 + d]^T wrench_k; tau[0:6] = b[0:6] - sum G_kv
+ * f_kv is the wrench the ground cannot supply, the feasibility signal.  info[e]
+ * = (|tau[0:3]|, |tau[3:6]|, max |x - z| over the components of every vertex in
+ * the last iteration, the number of vertices with f.n > 0).  efforts as in
+ * tg_contact_inverse_dynamics.  Every element of every non-NULL output is
+ * written; with fix_base the full layout is written too.  All lever arms are
+ * formed relative to the root link's origin: the result is bit-identical
+ * wherever the env sits on the grid.
+ *
+ * TG_ERR_ARG (message "tg_contact_qp: ...", nothing launched) for a null sim,
+ * null contacts, null extents, num_contacts outside 1..TG_CID_MAX_CONTACTS, a
+ * link outside [0, L), a link listed twice, an extent not finite or < 0, mu not
+ * finite or < 0, moment_arm not finite or <= 0, reg or rho not finite or <= 0,
+ * relax outside (0, 2), iters outside 1..TG_QP_MAX_ITERS, tau, wrench, forces,
+ * info and efforts all NULL, and every argument error of tg_inverse_dynamics
+ * on the arguments the two share.  A rejected call launches nothing.  Every
+ * model, run-time (tg_model_jit) ones included. */
+#define TG_QP_MAX_ITERS 256
+int tg_contact_qp(tg_sim *sim, const tg_contact_frame *contacts /* HOST */, int32_t num_contacts,
+                  const float *extents /* HOST [K][2] */,
+                  const float *normals /* [N, K, 3] device or NULL (= world z) */,
+                  const float *friction /* [N, K] device or NULL (= mu) */, float mu,
+                  const float *share /* [N, K] device or NULL (= 1) */,
+                  float moment_arm, float reg, float rho, float relax, int32_t iters,
+                  int32_t terms, const float *accel /* [N, 6+D] or NULL */,
+                  float *tau /* [N, 6+D] device or NULL */,
+                  float *wrench /* [N, K, 6] device or NULL */,
+                  float *forces /* [N, K, 4, 3] device or NULL */,
+                  float *info /* [N, 4] device or NULL */,
+                  float *efforts /* [N, D] device or NULL */,
+                  const int32_t *dofs /* HOST */, int32_t num_dofs, int32_t accumulate);
 /* fetch_results(sim, True): waits for the sim stream.  Also reports (once, as
  * TG_ERR_STATE) a state error a kernel raised since the last call: a locked
  * DOF whose [lower, upper] window was widened beyond TG_LOCK_WINDOW_MAX. */

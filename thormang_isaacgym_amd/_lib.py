@@ -58,6 +58,9 @@ SIGNATURES = {
                     C.POINTER(abi.tg_ray_params), _VP, _VP],
     "tg_proximity": [_VP, C.POINTER(abi.tg_capsule), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                      C.POINTER(abi.tg_proximity_params), _VP, _VP, _VP],
+    "tg_contact_qp": [_VP, C.POINTER(abi.tg_contact_frame), C.c_int32, C.POINTER(C.c_float), _VP, _VP, C.c_float, _VP,
+                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                      C.POINTER(C.c_int32), C.c_int32, C.c_int32],
     "tg_sync": [_VP],
     "tg_philox4x32_10": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "tg_rng_fill": [_VP, C.c_int32, C.c_uint64, C.c_uint64, _VP, C.c_int32],

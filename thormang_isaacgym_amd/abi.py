@@ -135,6 +135,10 @@ class tg_proximity_params(C.Structure):
 
 assert C.sizeof(tg_capsule) == 32 and C.sizeof(tg_proximity_params) == 4
 
+TG_QP_MAX_ITERS = 256                   # iterations of one tg_contact_qp call (its contacts: TG_CID_MAX_CONTACTS)
+# the ADMM parameters Sim.contact_qp passes by default (tgsim.h tg_contact_qp; DESIGN.md 4.2 has their provenance)
+TG_QP_DEFAULTS = {"reg": 0.03, "rho": 0.6, "relax": 1.6, "iters": 64}
+
 
 class tg_osc_gains(C.Structure):
     """The gains of tg_osc (tgsim.h): task-space kp / kd, null-space kp_null / kd_null, the damping lambda."""

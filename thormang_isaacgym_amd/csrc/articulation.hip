@@ -231,6 +231,14 @@ int launch_proximity(uint64_t hash, const float *root, const float *dof, int n, 
     return on_demand<OD_PROX>(hash, n, 64, stream, root, dof, n, pa, dist, witness, summary);
 }
 
+int launch_contact_qp(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props,
+                      int n, const IdArgs &ia, const QpArgs &qa, const float *normals, const float *friction,
+                      const float *share, const float *accel, float *tau, float *wrench, float *forces, float *info,
+                      float *efforts, hipStream_t stream) {
+    return on_demand<OD_QP>(hash, n, 64, stream, root, dof, mass_scale, props, n, ia, qa, normals, friction, share,
+                            accel, tau, wrench, forces, info, efforts);
+}
+
 int launch_rb_forces(uint64_t hash, const float *root, const float *dof, const float *comp, int n,
                      const float *mass_scale, const float *forces, const float *torques, int space, float *out,
                      const float *props, hipStream_t stream) {

@@ -1843,6 +1843,354 @@ __global__ __launch_bounds__(64) void contact_inverse_dynamics_kernel(const floa
     }
 }
 
+// all-reductions over the 4 lanes of a quad and the 16 lanes of a DPP row (quad swaps, row_half_mirror, row_mirror):
+// each step is symmetric, so every lane ends with the same bits; no LDS round trip.  Every lane of these
+// permutations has a valid source (mov_dpp with bound_ctrl, as step_par.h dpp)
+template <int CTRL> __device__ __forceinline__ float qp_dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float qp_sum4(float v) {
+    v += qp_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += qp_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
+    return v;
+}
+__device__ __forceinline__ float qp_sum16(float v) {
+    v = qp_sum4(v);
+    v += qp_dpp<0x141>(v);   // row_half_mirror: lane i <-> 7 - i
+    v += qp_dpp<0x140>(v);   // row_mirror: lane i <-> 15 - i
+    return v;
+}
+__device__ __forceinline__ float qp_max16(float v) {
+    v = fmaxf(v, qp_dpp<0xB1>(v));
+    v = fmaxf(v, qp_dpp<0x4E>(v));
+    v = fmaxf(v, qp_dpp<0x141>(v));
+    return fmaxf(v, qp_dpp<0x140>(v));
+}
+// finite, judged on the bits: the units of these kernels are built with fast-math, which may fold isfinite away
+__device__ __forceinline__ bool qp_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+// v, with a negative value and NaN taken as 0 (a share, a friction coefficient)
+__device__ __forceinline__ float qp_nonneg(float v) {
+    const uint32_t b = __float_as_uint(v);
+    return (b >> 31) || (b & 0x7fffffffu) > 0x7f800000u ? 0.f : v;
+}
+
+// Contact force distribution inside friction cones and sole outlines (tgsim.h tg_contact_qp): b = H a + h as
+// inverse_dynamics_kernel forms it, the vertex forces of the K rectangular contact patches that come nearest to
+// balancing b[0:6] while each stays in its friction cone -- the header's over-relaxed ADMM, a fixed number of
+// iterations from z = u = 0 -- and the joint torques that are left.  One wavefront per env:
+//   lanes        forward kinematics, the outward pass, the per-link wrenches W[l] about the root origin and their
+//                whole-body total, exactly as contact_inverse_dynamics_kernel
+//   lane & 15    = vertex j = 4 k + v of contact k (the four 16-lane rows carry the same values; row 0 stores): the
+//                lever arm r from the root com, the unit normal n, mu, 1 / (reg / s_k + rho) -- 0 for a lane past 4 K
+//                and for s_k = 0, whose vertex then stays at exactly 0.0 and adds exact zeros to every sum -- and
+//                c = G_j^T W b[0:6], all in registers
+//   every lane   the 6 x 6 matrix W^-1 + G P^-1 G^T from ten row sums (sum P^-1, sum P^-1 r, sum P^-1 r r^T) and its
+//                Cholesky factor, once
+//   the loop     q = c + rho (z - u), t = P^-1 q; G t by six row sums over the DPP row; the two triangular solves in
+//                every lane; x, the relaxation, the closed-form projection on the cone, u.  No LDS access and no
+//                barrier in the loop
+//   quads        each contact's wrench about p_k by two quad steps, to LDS about p_k and about the root origin
+//   lanes 0..5   the wrenches subtracted from W[l_k]; then the subtree sums, the projection on the joint axes,
+//                armature, tau and efforts as contact_inverse_dynamics_kernel; tau[0:6] is what the cones leave of b
+// An env with every share 0 skips the loop: forces 0.0, tau = b.  Wave-level syncs only, plain stores, no atomics.
+template <class M>
+__global__ __launch_bounds__(64) void contact_qp_kernel(const float *root, const float *dof, const float *mass_scale,
+                                                        const float *props, int n, IdArgs ia, QpArgs qa,
+                                                        const float *normals, const float *friction,
+                                                        const float *share, const float *accel, float *tau,
+                                                        float *wrench, float *forces, float *info, float *efforts) {
+    static_assert(M::link_parent[0] < 0, "link 0 is the root");
+    static_assert(4 * TG_CID_MAX_CONTACTS == 16, "one DPP row carries the vertices");
+    using JT = JacTables<M>;
+    constexpr int C = 6 + M::ND, MK = TG_CID_MAX_CONTACTS;
+    const int e = blockIdx.x;
+    if (e >= n) return;
+    __shared__ float T[M::NL][12], A[M::NL][3], V[M::NL][9], W[M::NL][6], B[6], LAM[MK][6], LAMO[MK][6];
+    const int lane = threadIdx.x;
+    auto wsync = [] {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    const float *r = root + 13 * (size_t)e, *q = dof + 2 * (size_t)e * M::ND;
+    const float *ac = accel ? accel + (size_t)e * C : nullptr;
+    const bool vel = (ia.terms & TG_ID_VELOCITY) != 0;
+    const V3 zero = v3(0.f, 0.f, 0.f);
+    const int K = qa.K < MK ? qa.K : MK;
+    // this lane's vertex, and what of it does not wait for the passes: the share, mu and the normal
+    const int vj = lane & 15, vk = vj >> 2, vv = vj & 3;
+    const bool mine = vk < K;
+    float sk = 0.f, mu = 0.f, S = 0.f;
+    V3 nv = v3(0.f, 0.f, 1.f);
+#pragma unroll
+    for (int k = 0; k < MK; ++k) {
+        if (k >= K) continue;
+        const float sh = share ? share[(size_t)e * K + k] : 1.f;
+        const float s = qp_nonneg(sh);
+        S += s;
+        sk = k == vk ? s : sk;
+    }
+    if (mine) {
+        const float m = friction ? friction[(size_t)e * K + vk] : qa.mu;
+        mu = fminf(qp_nonneg(m), 1e6f);
+        if (normals) {
+            const float *np = normals + ((size_t)e * K + vk) * 3;
+            const float nx = np[0], ny = np[1], nz = np[2];
+            if (qp_finite(nx) && qp_finite(ny) && qp_finite(nz)) {
+                // (scaled by the largest component first: the square of a large entry stays finite)
+                const float big = fmaxf(fabsf(nx), fmaxf(fabsf(ny), fabsf(nz)));
+                if (big >= 1e-6f * 0.57735026f) {
+                    const float ib = 1.0f / big, ax = nx * ib, ay = ny * ib, az = nz * ib;
+                    const float len = sqrtf(ax * ax + ay * ay + az * az);
+                    if (len * big >= 1e-6f) nv = (1.0f / len) * v3(ax, ay, az);
+                }
+            }
+        }
+    }
+    fk_root_relative<M>(r, q, lane, T, A);
+    // the root link's com relative to its origin, world axes
+    V3 c0;
+    {
+        M3 R0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R0.a[k] = T[0][k];
+        c0 = mul(R0, v3(M::link_inertia[0][1], M::link_inertia[0][2], M::link_inertia[0][3]));
+    }
+    constexpr int NP = (M::NL + 63) / 64;   // links per lane
+    for (int lev = 0; lev <= M::NDEPTH; ++lev) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int l = lane + 64 * p;
+            if (l >= M::NL || M::link_depth[l] != lev) continue;
+            const int pl = M::link_parent[l];
+            V3 w, al, ao;
+            if (pl < 0) {
+                w = vel ? v3(r[10], r[11], r[12]) : zero;
+                al = ac ? v3(ac[3], ac[4], ac[5]) : zero;
+                V3 acom = ac ? v3(ac[0], ac[1], ac[2]) : zero;
+                if (ia.terms & TG_ID_GRAVITY) acom = acom - v3(ia.g[0], ia.g[1], ia.g[2]);
+                ao = acom - cross(al, c0) - cross(w, cross(w, c0));
+            } else {
+                const V3 wp = v3(V[pl][0], V[pl][1], V[pl][2]), alp = v3(V[pl][3], V[pl][4], V[pl][5]);
+                const V3 rr = v3(T[l][9], T[l][10], T[l][11]) - v3(T[pl][9], T[pl][10], T[pl][11]);
+                const int d = M::link_dof[l];
+                const float qd = d >= 0 && vel ? q[2 * d + 1] : 0.f, qdd = d >= 0 && ac ? ac[6 + d] : 0.f;
+                const V3 a = v3(A[l][0], A[l][1], A[l][2]);
+                w = wp;
+                al = alp;
+                ao = v3(V[pl][6], V[pl][7], V[pl][8]) + cross(alp, rr) + cross(wp, cross(wp, rr));
+                if (M::link_jtype[l] == TG_JOINT_REVOLUTE) {
+                    w = w + qd * a;
+                    al = al + qdd * a + cross(wp, qd * a);
+                } else if (M::link_jtype[l] == TG_JOINT_PRISMATIC) {
+                    ao = ao + qdd * a + 2.f * cross(wp, qd * a);
+                }
+            }
+            V[l][0] = w.x; V[l][1] = w.y; V[l][2] = w.z;
+            V[l][3] = al.x; V[l][4] = al.y; V[l][5] = al.z;
+            V[l][6] = ao.x; V[l][7] = ao.y; V[l][8] = ao.z;
+        }
+        wsync();
+    }
+    // every link's force and its moment about the root origin, mass-scaled
+    for (int l = lane; l < M::NL; l += 64) {
+        M3 R;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R.a[k] = T[l][k];
+        const float *li = M::link_inertia[l];
+        const float sc = mass_scale ? mass_scale[(size_t)e * M::NL + l] : 1.f;
+        const V3 rc = mul(R, v3(li[1], li[2], li[3])), c = v3(T[l][9], T[l][10], T[l][11]) + rc;
+        float I[6];
+        sym_rot(li + 4, transpose(R), I);   // R I R^T
+        const V3 w = v3(V[l][0], V[l][1], V[l][2]), al = v3(V[l][3], V[l][4], V[l][5]);
+        const V3 acom = v3(V[l][6], V[l][7], V[l][8]) + cross(al, rc) + cross(w, cross(w, rc));
+        const V3 f = (sc * li[0]) * acom;
+        const V3 nn = sc * (symmul(I, al) + cross(w, symmul(I, w))) + cross(c, f);
+        W[l][0] = f.x; W[l][1] = f.y; W[l][2] = f.z;
+        W[l][3] = nn.x; W[l][4] = nn.y; W[l][5] = nn.z;
+    }
+    wsync();
+    // the whole body's force and moment about the root origin
+    if (lane < 6) {
+        float t = W[0][lane];
+        for (int l = 1; l < M::NL; ++l) t += W[l][lane];
+        B[lane] = t;
+    }
+    wsync();
+    // this lane's vertex: the contact point pk, the vertex from it (dv) and from the root com (rv)
+    V3 pk = zero, dv = zero;
+    {
+        int link = 0;
+        V3 off = zero;
+        float hx = 0.f, hy = 0.f;
+#pragma unroll
+        for (int k = 0; k < MK; ++k) {
+            if (k >= K || k != vk) continue;
+            link = qa.c[k].link;
+            off = v3(qa.c[k].offset[0], qa.c[k].offset[1], qa.c[k].offset[2]);
+            hx = qa.ext[k][0];
+            hy = qa.ext[k][1];
+        }
+        M3 R;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R.a[i] = T[link][i];
+        // v = 0..3: (+, +), (+, -), (-, -), (-, +)
+        const V3 corner = v3(vv < 2 ? hx : -hx, (vv == 0 || vv == 3) ? hy : -hy, 0.f);
+        if (mine) {
+            pk = v3(T[link][9], T[link][10], T[link][11]) + mul(R, off);
+            dv = mul(R, corner);
+        }
+    }
+    const V3 rv = pk + dv - c0;
+    const float il2 = 1.0f / qa.arm2;
+    const V3 bf = v3(B[0], B[1], B[2]);
+    const V3 bn = v3(B[3], B[4], B[5]) - cross(c0, bf);   // the moment about the root com
+    V3 z = zero;
+    float res = 0.f;
+    if (S > 0.f) {
+        const float pinv = mine && sk > 0.f ? 1.0f / (qa.reg / sk + qa.rho) : 0.f;
+        const V3 cv = bf + cross(il2 * bn, rv);   // G_j^T W b[0:6]
+        // W^-1 + G P^-1 G^T, lower triangle by rows, and its factor L (the diagonal kept inverted)
+        float L[21];
+        {
+            const float sp = qp_sum16(pinv);
+            const V3 mr = v3(qp_sum16(pinv * rv.x), qp_sum16(pinv * rv.y), qp_sum16(pinv * rv.z));
+            const float xx = qp_sum16(pinv * rv.x * rv.x), yy = qp_sum16(pinv * rv.y * rv.y),
+                        zz = qp_sum16(pinv * rv.z * rv.z), xy = qp_sum16(pinv * rv.x * rv.y),
+                        xz = qp_sum16(pinv * rv.x * rv.z), yz = qp_sum16(pinv * rv.y * rv.z);
+            const float d = 1.0f + sp;
+            const float g[21] = {d,
+                                 0.f, d,
+                                 0.f, 0.f, d,
+                                 0.f, -mr.z, mr.y, qa.arm2 + yy + zz,
+                                 mr.z, 0.f, -mr.x, -xy, qa.arm2 + xx + zz,
+                                 -mr.y, mr.x, 0.f, -xz, -yz, qa.arm2 + xx + yy};
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                float dj = g[j * (j + 1) / 2 + j];
+#pragma unroll
+                for (int k = 0; k < j; ++k) dj -= L[j * (j + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+                const float inv = 1.0f / sqrtf(dj);
+                L[j * (j + 1) / 2 + j] = inv;
+#pragma unroll
+                for (int i = j + 1; i < 6; ++i) {
+                    float s = g[i * (i + 1) / 2 + j];
+#pragma unroll
+                    for (int k = 0; k < j; ++k) s -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+                    L[i * (i + 1) / 2 + j] = s * inv;
+                }
+            }
+        }
+        V3 u = zero;
+        const float imu2 = 1.0f / (1.0f + mu * mu);
+        for (int it = 0; it < qa.iters; ++it) {
+            const V3 t = pinv * (cv + qa.rho * (z - u));
+            const V3 mt = cross(rv, t);
+            float y[6] = {qp_sum16(t.x), qp_sum16(t.y), qp_sum16(t.z), qp_sum16(mt.x), qp_sum16(mt.y), qp_sum16(mt.z)};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {   // L w = G t
+                float s = y[i];
+#pragma unroll
+                for (int k = 0; k < i; ++k) s -= L[i * (i + 1) / 2 + k] * y[k];
+                y[i] = s * L[i * (i + 1) / 2 + i];
+            }
+#pragma unroll
+            for (int i = 5; i >= 0; --i) {   // L^T y = w
+                float s = y[i];
+#pragma unroll
+                for (int k = i + 1; k < 6; ++k) s -= L[k * (k + 1) / 2 + i] * y[k];
+                y[i] = s * L[i * (i + 1) / 2 + i];
+            }
+            const V3 x = t - pinv * (v3(y[0], y[1], y[2]) + cross(v3(y[3], y[4], y[5]), rv));
+            const V3 xh = qa.relax * x + (1.0f - qa.relax) * z;
+            const V3 w = xh + u;
+            // the projection on the cone { f.n >= 0, |f - (f.n) n| <= mu f.n }
+            const float fn = dot(w, nv);
+            const V3 wt = w - fn * nv;
+            const float tn = sqrtf(dot(wt, wt));
+            if (fn >= 0.f && tn <= mu * fn) {
+                z = w;
+            } else if (mu * tn <= -fn) {
+                z = zero;
+            } else {
+                const float a = (mu * tn + fn) * imu2;
+                z = a * (nv + (mu / fmaxf(tn, 1e-30f)) * wt);
+            }
+            if (pinv == 0.f) z = zero;
+            u = u + xh - z;
+            const V3 dx = x - z;
+            res = fmaxf(fabsf(dx.x), fmaxf(fabsf(dx.y), fabsf(dx.z)));
+        }
+        res = qp_max16(res);
+    }
+    // each contact's wrench: about p_k (what is returned) and about the root origin (what its link loses)
+    {
+        const V3 mz = cross(dv, z);
+        const V3 fk = v3(qp_sum4(z.x), qp_sum4(z.y), qp_sum4(z.z));
+        const V3 mk = v3(qp_sum4(mz.x), qp_sum4(mz.y), qp_sum4(mz.z));
+        if (lane < 16 && mine && vv == 0) {
+            const V3 mo = mk + cross(pk, fk);
+            LAM[vk][0] = fk.x; LAM[vk][1] = fk.y; LAM[vk][2] = fk.z;
+            LAM[vk][3] = mk.x; LAM[vk][4] = mk.y; LAM[vk][5] = mk.z;
+            LAMO[vk][0] = fk.x; LAMO[vk][1] = fk.y; LAMO[vk][2] = fk.z;
+            LAMO[vk][3] = mo.x; LAMO[vk][4] = mo.y; LAMO[vk][5] = mo.z;
+        }
+    }
+    const float up = qp_sum16(mine && dot(z, nv) > 0.f ? 1.f : 0.f);
+    if (forces && lane < 4 * K) {
+        float *fo = forces + ((size_t)e * 4 * K + lane) * 3;
+        fo[0] = z.x; fo[1] = z.y; fo[2] = z.z;
+    }
+    wsync();
+    if (lane < 6) {
+        // lane t carries float t of every wrench about the root origin, then of the subtree sums
+#pragma unroll
+        for (int k = 0; k < MK; ++k) {
+            if (k >= K) continue;
+            W[qa.c[k].link][lane] -= LAMO[k][lane];
+        }
+#pragma unroll
+        for (int k = M::NL - 1; k >= 1; --k) W[M::link_parent[k]][lane] += W[k][lane];
+    }
+    wsync();
+    if (wrench && lane < 6 * K) wrench[((size_t)e * K) * 6 + lane] = LAM[lane / 6][lane % 6];
+    float *to = tau ? tau + (size_t)e * C : nullptr;
+    for (int d = lane; d < M::ND; d += 64) {
+        const int j = JT::dof_link.v[d];
+        const V3 a = v3(A[j][0], A[j][1], A[j][2]), fj = v3(W[j][0], W[j][1], W[j][2]);
+        float t;
+        if (M::link_jtype[j] == TG_JOINT_PRISMATIC)
+            t = dot(a, fj);
+        else
+            t = dot(a, v3(W[j][3], W[j][4], W[j][5]) - cross(v3(T[j][9], T[j][10], T[j][11]), fj));
+        if (ac) t += props[((size_t)TG_PROP_ARMATURE * n + e) * M::ND + d] * ac[6 + d];
+        if (to) to[6 + d] = t;
+        if (efforts && d < 32 * TG_ID_MASK_WORDS && ((ia.mask[d >> 5] >> (d & 31)) & 1u)) {
+            const float lim = props[((size_t)TG_PROP_EFFORT * n + e) * M::ND + d];
+            float *o = efforts + (size_t)e * M::ND + d;
+            const float sum = ia.accumulate ? *o + t : t;
+            *o = fminf(fmaxf(sum, -lim), lim);
+        }
+    }
+    if ((to || info) && lane < 6) {
+        // the base rows: what the cones leave of the whole body's force and of its moment about the root com
+        const V3 fr = v3(W[0][0], W[0][1], W[0][2]);
+        const V3 nc = v3(W[0][3], W[0][4], W[0][5]) - cross(c0, fr);
+        const float o[6] = {fr.x, fr.y, fr.z, nc.x, nc.y, nc.z};
+        float v = o[0];
+#pragma unroll
+        for (int k = 1; k < 6; ++k) v = lane == k ? o[k] : v;
+        if (to) to[lane] = v;
+        if (info && lane < 4) {
+            const float o4[4] = {sqrtf(dot(fr, fr)), sqrtf(dot(nc, nc)), res, up};
+            float v4 = o4[0];
+#pragma unroll
+            for (int k = 1; k < 4; ++k) v4 = lane == k ? o4[k] : v4;
+            info[(size_t)e * 4 + lane] = v4;
+        }
+    }
+}
+
 // Centroidal quantities (tgsim.h tg_centroidal): the whole-body centre of mass
 // c, its velocity, the angular momentum k about it, the total mass M and the
 // centroidal inertia I_G into state [N, 16]; the centroidal momentum matrix A

@@ -152,7 +152,7 @@ int compile(const std::string &src, const std::string &incdir, JitCode &out, std
     return 0;
 }
 
-// cache file: "TGJIT11\n", one lowered name per line, then the code object
+// cache file: "TGJIT12\n", one lowered name per line, then the code object
 bool cache_load(const std::string &path, JitCode &out) {
     std::string s;
     if (!read_file(path, s)) return false;
@@ -165,7 +165,7 @@ bool cache_load(const std::string &path, JitCode &out) {
         return true;
     };
     std::string magic;
-    if (!line(magic) || magic != "TGJIT11") return false;
+    if (!line(magic) || magic != "TGJIT12") return false;
     for (int k = 0; k < NK; ++k)
         if (!line(out.names[k]) || out.names[k].empty()) return false;
     if (pos >= s.size()) return false;
@@ -178,7 +178,7 @@ void cache_store(const std::string &path, const JitCode &c) {
     {
         std::ofstream f(tmp, std::ios::binary);
         if (!f) return;
-        f << "TGJIT11\n";
+        f << "TGJIT12\n";
         for (int k = 0; k < NK; ++k) f << c.names[k] << "\n";
         f.write(c.code.data(), (std::streamsize)c.code.size());
         if (!f) return;

@@ -39,6 +39,16 @@ struct CidArgs {
     int K;
     float arm2;
 };
+// what a tg_contact_qp call hands contact_qp_kernel by value beside its IdArgs: the K contact frames, the half
+// extents (hx, hy) of their patches in the link's x and y axes, the squared moment arm, the scalar friction
+// coefficient (read where the friction tensor is null) and the ADMM parameters of the header
+struct QpArgs {
+    tg_contact_frame c[TG_CID_MAX_CONTACTS];
+    float ext[TG_CID_MAX_CONTACTS][2];
+    int K;
+    float arm2, mu, reg, rho, relax;
+    int iters;
+};
 
 // what a tg_height_scan call hands height_scan_kernel by value: the frames, the counts, tg_scan_params and the
 // sim's heightfield at the time of the call under the member names of StepArgs, which ground_at (ground.h) reads
@@ -264,7 +274,8 @@ constexpr int JAC_THREADS = 256;   // threads per env of jacobian_kernel
     X(SCAN, height_scan_kernel)                    \
     X(IMU, imu_kernel)                             \
     X(RAY, ray_cast_kernel)                        \
-    X(PROX, proximity_kernel)
+    X(PROX, proximity_kernel)                      \
+    X(QP, contact_qp_kernel)
 #define TG_OD_ENUM(ID, KERNEL) OD_##ID,
 enum OnDemandKernel { TG_FOR_EACH_ON_DEMAND(TG_OD_ENUM) OD_COUNT };
 #undef TG_OD_ENUM
@@ -317,6 +328,12 @@ int launch_contact_inverse_dynamics(uint64_t hash, const float *root, const floa
                                     const float *props, int n, const IdArgs &ia, const CidArgs &ca, const float *share,
                                     const float *accel, float *tau, float *wrench, float *efforts,
                                     hipStream_t stream);
+// contact forces in their friction cones: tau [N, 6 + D], the contact wrenches [N, K, 6], the vertex forces
+// [N, K, 4, 3], info [N, 4] and / or efforts [N, D] (contact_qp_kernel; tgsim.h tg_contact_qp)
+int launch_contact_qp(uint64_t hash, const float *root, const float *dof, const float *mass_scale, const float *props,
+                      int n, const IdArgs &ia, const QpArgs &qa, const float *normals, const float *friction,
+                      const float *share, const float *accel, float *tau, float *wrench, float *forces, float *info,
+                      float *efforts, hipStream_t stream);
 // centroidal state [N, 16], momentum matrix [N, 6, 6 + D] and momentum-rate bias [N, 6], each optional
 // (centroidal_kernel; tgsim.h tg_centroidal)
 int launch_centroidal(uint64_t hash, const float *root, const float *dof, const float *mass_scale, int n, float *state,

@@ -935,6 +935,63 @@ int tg_contact_inverse_dynamics(tg_sim *s, const tg_contact_frame *contacts, int
     return TG_OK;
 }
 
+int tg_contact_qp(tg_sim *s, const tg_contact_frame *contacts, int32_t num_contacts, const float *extents,
+                  const float *normals, const float *friction, float mu, const float *share, float moment_arm,
+                  float reg, float rho, float relax, int32_t iters, int32_t terms, const float *accel, float *tau,
+                  float *wrench, float *forces, float *info, float *efforts, const int32_t *dofs, int32_t num_dofs,
+                  int32_t accumulate) {
+    const char *fn = "tg_contact_qp";
+    if (!s) return fail(TG_ERR_ARG, "%s: null tg_sim", fn);
+    if (!contacts) return fail(TG_ERR_ARG, "%s: null contacts", fn);
+    if (!extents) return fail(TG_ERR_ARG, "%s: null extents", fn);
+    if (num_contacts < 1 || num_contacts > TG_CID_MAX_CONTACTS)
+        return fail(TG_ERR_ARG, "%s: num_contacts %d outside 1..%d", fn, num_contacts, TG_CID_MAX_CONTACTS);
+    tg::QpArgs qa{};
+    for (int k = 0; k < num_contacts; ++k) {
+        const int l = contacts[k].link;
+        if (l < 0 || l >= s->L) return fail(TG_ERR_ARG, "%s: contact %d: link %d outside [0, %d)", fn, k, l, s->L);
+        for (int j = 0; j < k; ++j)
+            if (contacts[j].link == l) return fail(TG_ERR_ARG, "%s: link %d appears twice", fn, l);
+        qa.c[k] = contacts[k];
+    }
+    for (int k = 0; k < num_contacts; ++k)
+        for (int i = 0; i < 2; ++i) {
+            const float h = extents[2 * k + i];
+            if (!(h >= 0.f) || !std::isfinite(h))
+                return fail(TG_ERR_ARG, "%s: contact %d: extent[%d] %g is not a finite number >= 0", fn, k, i, (double)h);
+            qa.ext[k][i] = h;
+        }
+    if (!(mu >= 0.f) || !std::isfinite(mu))
+        return fail(TG_ERR_ARG, "%s: mu %g is not a finite number >= 0", fn, (double)mu);
+    if (!(moment_arm > 0.f) || !std::isfinite(moment_arm))
+        return fail(TG_ERR_ARG, "%s: moment_arm %g is not a finite number > 0", fn, (double)moment_arm);
+    if (!(reg > 0.f) || !std::isfinite(reg))
+        return fail(TG_ERR_ARG, "%s: reg %g is not a finite number > 0", fn, (double)reg);
+    if (!(rho > 0.f) || !std::isfinite(rho))
+        return fail(TG_ERR_ARG, "%s: rho %g is not a finite number > 0", fn, (double)rho);
+    if (!(relax > 0.f && relax < 2.f)) return fail(TG_ERR_ARG, "%s: relax %g outside (0, 2)", fn, (double)relax);
+    if (iters < 1 || iters > TG_QP_MAX_ITERS)
+        return fail(TG_ERR_ARG, "%s: iters %d outside 1..%d", fn, iters, TG_QP_MAX_ITERS);
+    if (int rc = check_id_terms(fn, terms, accel)) return rc;
+    if (!tau && !wrench && !forces && !info && !efforts)
+        return fail(TG_ERR_ARG, "%s: tau, wrench, forces, info and efforts are all null", fn);
+    tg::IdArgs ia{};
+    if (int rc = check_id_dofs(s, fn, terms, efforts, dofs, num_dofs, accumulate, ia)) return rc;
+    qa.K = num_contacts;
+    qa.arm2 = moment_arm * moment_arm;
+    qa.mu = mu;
+    qa.reg = reg;
+    qa.rho = rho;
+    qa.relax = relax;
+    qa.iters = iters;
+    DeviceGuard dg(s->device);
+    win_touch(s);
+    if (int rc = tg::launch_contact_qp(s->hash, s->root, s->dof, s->mass_scale, s->props, (int)s->N, ia, qa, normals,
+                                       friction, share, accel, tau, wrench, forces, info, efforts, s->stream))
+        return fail(rc, "%s: launch failed", fn);
+    return TG_OK;
+}
+
 int tg_centroidal(tg_sim *s, float *state, float *matrix, float *bias) {
     if (!s) return fail(TG_ERR_ARG, "tg_centroidal: null tg_sim");
     if (!state && !matrix && !bias) return fail(TG_ERR_ARG, "tg_centroidal: state, matrix and bias are all null");

@@ -140,6 +140,7 @@ def _ptr(t: torch.Tensor | None):
 
 Centroidal = namedtuple("Centroidal", ["state", "matrix", "bias"])   # what Sim.centroidal returns
 ContactDynamics = namedtuple("ContactDynamics", ["tau", "wrench"])   # what Sim.contact_inverse_dynamics returns
+ContactForces = namedtuple("ContactForces", ["tau", "wrench", "forces", "info"])   # what Sim.contact_qp returns
 HeightScan = namedtuple("HeightScan", ["heights", "normals"])   # what Sim.height_scan returns
 RayCast = namedtuple("RayCast", ["dist", "normals"])   # what Sim.ray_cast returns
 Proximity = namedtuple("Proximity", ["dist", "witness", "summary"])   # what Sim.proximity returns
@@ -781,6 +782,84 @@ class Sim:
                                                 _ptr(out), _ptr(wrench), _ptr(efforts), arr, len(idx),
                                                 1 if accumulate else 0), "contact_inverse_dynamics")
         return ContactDynamics(out, wrench)
+
+    def contact_qp(self, contacts, extents, mu: float = 0.7, friction: torch.Tensor | None = None,
+                   normals: torch.Tensor | None = None, share: torch.Tensor | None = None,
+                   accel: torch.Tensor | None = None, gravity: bool = True, velocity: bool = True,
+                   moment_arm: float = 0.1, reg: float = abi.TG_QP_DEFAULTS["reg"],
+                   rho: float = abi.TG_QP_DEFAULTS["rho"], relax: float = abi.TG_QP_DEFAULTS["relax"],
+                   iters: int = abi.TG_QP_DEFAULTS["iters"], forces: bool = False, info: bool = False,
+                   efforts: torch.Tensor | None = None, dofs=None, accumulate: bool = False) -> "ContactForces":
+        """``contact_inverse_dynamics`` with contact forces the ground can
+        supply, in one kernel launch (tgsim.h tg_contact_qp).  Each of the K
+        ``contacts`` (``contact_frame``, at most 4) is a rectangular patch with
+        half extents ``extents[k] = (hx, hy)`` in the link's x and y axes about
+        the frame's offset ((0, 0): a point); ``walk_sole_patch`` gives a foot's.
+        The forces at the 4 K patch vertices are confined to the friction cone
+        of their contact -- normal ``normals`` [N, K, 3] (None: world z; e.g.
+        ``height_scan(normals=True)``), coefficient ``friction`` [N, K] or the
+        scalar ``mu`` -- and come as near to balancing the base rows of ``b = H
+        a + h`` as the cones allow, by ``iters`` iterations of the header's ADMM
+        (``reg``, ``rho``, ``relax``), every returned force feasible after any
+        number of them.  ``share`` [N, K] weighs the contacts (0 removes one
+        exactly).  Returns ``ContactForces(tau, wrench, forces, info)``:
+        ``tau`` [N, 6 + D] with the joint torques in ``tau[:, 6:]`` and the
+        base wrench the ground cannot supply in ``tau[:, :6]``; ``wrench`` [N,
+        K, 6] (force, moment about the contact point) in the convention of
+        ``contact_inverse_dynamics``; with ``forces`` the vertex forces [N, K,
+        4, 3]; with ``info`` [N, 4]: ``|tau[:3]|``, ``|tau[3:6]|``, the last
+        iteration's ``max |x - z|`` and the number of loaded vertices; a part
+        not requested is None.  The tensors are owned by the sim and
+        overwritten by the next call with as many contacts.  ``accel``,
+        ``gravity``, ``velocity``, ``moment_arm``, ``efforts``, ``dofs`` and
+        ``accumulate`` as in ``contact_inverse_dynamics``."""
+        def checked(t, shape, what):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != "cuda" or \
+                    t.device.index != (self.device.index or 0):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous with shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        contacts = list(contacts)
+        K = len(contacts)
+        if not 1 <= K <= abi.TG_CID_MAX_CONTACTS:
+            raise ValueError(f"contact_qp takes 1..{abi.TG_CID_MAX_CONTACTS} contacts, got {K}")
+        contacts = [c if isinstance(c, abi.tg_contact_frame) else self.contact_frame(c) for c in contacts]
+        ext = [tuple(float(v) for v in x) for x in extents]
+        if len(ext) != K or any(len(x) != 2 for x in ext):
+            raise ValueError(f"extents must be {K} pairs (hx, hy), got {extents!r}")
+        N, C_ = self.num_envs, 6 + self.D
+        for t, shape, what in ((friction, (N, K), "friction"), (normals, (N, K, 3), "normals"), (share, (N, K), "share"),
+                               (accel, (N, C_), "accel"), (efforts, (N, self.D), "efforts")):
+            if t is not None:
+                checked(t, shape, what)
+        own = getattr(self, "_qp_out", None)
+        if own is None:
+            own = self._qp_out = {}
+
+        def owned(key, shape):
+            if key not in own:
+                own[key] = torch.zeros(*shape, dtype=torch.float32, device=self.device)
+            return own[key]
+
+        tau, wrench = owned("tau", (N, C_)), owned(("wrench", K), (N, K, 6))
+        fo = owned(("forces", K), (N, K, 4, 3)) if forces else None
+        io = owned("info", (N, 4)) if info else None
+        terms = (abi.TG_ID_GRAVITY if gravity else 0) | (abi.TG_ID_VELOCITY if velocity else 0)
+        if terms == 0 and accel is None:
+            raise ValueError("contact_qp without gravity, velocity and accel has nothing to compute")
+        idx = [] if dofs is None else [self._name_index("dof", x) for x in dofs]
+        if dofs is not None and not idx:
+            raise ValueError("dofs is empty; pass None for every DOF")
+        arr = (C.c_int32 * len(idx))(*idx) if idx else None
+        frames = (abi.tg_contact_frame * K)(*contacts)
+        hxy = (C.c_float * (2 * K))(*[v for x in ext for v in x])
+        check(lib().tg_contact_qp(self._h, frames, K, hxy, _ptr(normals), _ptr(friction), float(mu), _ptr(share),
+                                  float(moment_arm), float(reg), float(rho), float(relax), int(iters), terms,
+                                  _ptr(accel), _ptr(tau), _ptr(wrench), _ptr(fo), _ptr(io), _ptr(efforts), arr,
+                                  len(idx), 1 if accumulate else 0), "contact_qp")
+        return ContactForces(tau, wrench, fo, io)
 
     def centroidal(self, matrix: bool = False, bias: bool = False, out: torch.Tensor | None = None,
                    out_matrix: torch.Tensor | None = None, out_bias: torch.Tensor | None = None) -> "Centroidal":

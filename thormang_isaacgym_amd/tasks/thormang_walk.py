@@ -397,6 +397,17 @@ def walk_sole_centre(m, link: int):
     return [float(v) for v in np.asarray(s.pos, np.float64) + float(s.params[k]) * down]
 
 
+def walk_sole_patch(m, link: int):
+    """The sole of foot ``link`` as a contact patch of ``Sim.contact_qp``:
+    ``(offset, (hx, hy))``, the sole's centre (``walk_sole_centre``) and the half
+    extents of its collision box along the link's x and y axes (the box's axes
+    are the link's up to a permutation)."""
+    s = next(s for s in m.shapes if m.link_index(s.link) == link and s.kind == "box")
+    rot = np.asarray(s.rot, np.float64).reshape(3, 3)
+    ix, iy = int(np.argmax(np.abs(rot[0]))), int(np.argmax(np.abs(rot[1])))
+    return walk_sole_centre(m, link), (float(s.params[ix]), float(s.params[iy]))
+
+
 def walk_asset_options(cfg) -> dict:
     ao = dict(cfg["env"].get("asset", {}))
     ao.setdefault("ground_friction", 1.0)
